@@ -13,11 +13,14 @@ Timed: upload of the initial states -> on-device solve of every instance -> (N >
 download of this rank's rows to the host.  `value` = instances that MET THE CONVERGENCE TEST |dL| < change_threshold
 (SCvxAlgorithm.cpp:125) summed over ranks / wall time (max over ranks).  Weak scaling: per-GPU work fixed.
 
-Secondary numbers (rank 0, outside the timed region) under `config`: the SC-mode (SCAlgorithm, what SC_oneshot runs) rate in
+A plain run sets up, warms up, times the steps, writes the outputs of the last timed step (--dump-outputs DIR) and prints the line:
+its roofline and kernel figures come from the timed job itself.  Secondary numbers take runs of their own and come with --full only
+(rank 0, outside the timed region, under `config` and `cpu_baseline`): the SC-mode (SCAlgorithm, what SC_oneshot runs) rate in
 trajectories TERMINATED per second -- with the shipped weights none of them meets SCAlgorithm's convergence test at K=50,
-see DESIGN.md -- an isolated single-batch SCvx solve, un-overlapped (single-pool) kernel times, and the linear-MPC leg.
+see DESIGN.md -- an isolated single-batch SCvx solve, un-overlapped (single-pool) kernel times, the other instantiations of the
+persistent kernel, the linear-MPC leg, what "converged" means for the returned trajectories, and the CPU baseline.
 
-Usage: python bench.py --gpus N --steps K --warmup W.  N > 1 without a launcher: the script starts its N ranks itself (one process per
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR].  N > 1 without a launcher: the script starts its N ranks itself (one process per
 GPU under torch.distributed.run on 127.0.0.1, `_self_launch`) and refuses when fewer than N GPUs are visible; under an external
 torch.distributed.run (WORLD_SIZE set) it is one of the ranks.  --backend gloo + --library <emulation build> drives the same N > 1
 code path on CPU in tests/test_bench_distributed.py, with and without the launcher.
@@ -194,6 +197,24 @@ def parity_summary():
     return out
 
 
+DUMP_BYTES_MAX = 64_000_000
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(out, lo, hi, directory):
+    """--dump-outputs: the arrays the caller of the timed path receives (stream_download: X, U and the per-instance scalars) for
+    the instances lo .. hi - 1 of the job -- the last timed step -- as float64 DIR/<name>.npy.  A step larger than DUMP_BYTES_MAX
+    is reduced to a fixed, seeded sample of its instances (the same sample every run; `instance` names them)."""
+    os.makedirs(directory, exist_ok=True)
+    per_instance = sum(int(np.prod(v.shape[1:])) * 8 for v in out.values())
+    idx = np.arange(lo, hi)
+    if per_instance * idx.size > DUMP_BYTES_MAX:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = np.sort(rng.choice(idx, DUMP_BYTES_MAX // per_instance, replace=False))
+    for name, v in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(v[idx], dtype=np.float64))
+
+
 def _self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: re-run this very command line as N ranks (one process per GPU) under
     torch.distributed.run on the loopback interface; the children see WORLD_SIZE / RANK / LOCAL_RANK and take the distributed path of
@@ -241,13 +262,21 @@ def main():
     ap.add_argument("--placement-candidates", type=int, default=None,
                     help="contexts allocated side by side, a short probe job on each, the best one kept (SCvxAlgorithm.initialize; DESIGN.md 5: the placement "
                          "regimes; measured in round 6: no gain on a box whose first allocation is already in the fast regime, profiles/r06_placement_regimes.json).  Default 1 = off.  Outside the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (SC mode, single batch, single pool, MPC)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (CPU baseline, SC mode, single batch, single pool, step-length rule, other "
+                         "instantiations, MPC, the dimensional check of converged trajectories); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary legs (SC mode, single batch, single pool, MPC)")
     ap.add_argument("--mpc-batch", type=int, default=32768)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the result arrays of its last timed step (X, U and the per-instance scalars of the streaming job) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded sample of the step's instances beyond that)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU under torch.distributed.run, loopback
         # rendezvous on a free port) and hand its exit code back.  Under an external launcher WORLD_SIZE is set and this is skipped.
@@ -377,9 +406,11 @@ def main():
         g_conv, g_total, g_iters, g_solves, g_ipm, g_fail = [float(v) for v in local]
         if args.dump:
             np.save(args.dump, gathered.cpu().numpy() if gathered is not None else ctx.stream_download_rows())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, total - B, total, args.dump_outputs)
 
     extras = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- what "converged" buys (north_star: "final virtual-control norm reported").  The reference's test is |dL| < change_threshold
         # (SCvxAlgorithm.cpp:125) and nothing else: it does NOT ask for nu -> 0, and a shrinking trust radius makes dL small.  Reported: how many converged
         # runs also meet the SC mode's nu_tol (1e-5), where the radius ended, and -- on the product's own simulate kernel, in SI units -- how far the
@@ -418,7 +449,7 @@ def main():
             extras["what_converged_means"] = meaning
         except Exception as e:
             extras["what_converged_means"] = {"error": str(e)}
-    if rank == 0 and world == 1 and not args.no_extras:  # (single-GPU runs only: at N > 1 the other ranks would idle behind these legs)
+    if rank == 0 and world == 1 and args.full and not args.no_extras:  # (single-GPU runs only: at N > 1 the other ranks would idle behind these legs)
         # ---- un-overlapped kernel times: the same engine with ONE slot pool (one stream), a 2-batch job ----
         try:
             ctx.timing(reset=True)
@@ -756,7 +787,7 @@ def main():
                 },
             },
         }
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             try:
                 line["cpu_baseline"] = cpu_baseline(K, args.seed)
             except Exception as e:  # the oracle is a checker; its absence must not hide the GPU number

@@ -135,6 +135,44 @@ def test_bench_force_gather_single_rank(model, emu_lib, tmp_path):
     assert np.array_equal(rg.view(np.uint64), rp.view(np.uint64))
 
 
+def test_bench_plain_run_dumps_its_last_step(emu_lib, tmp_path):
+    """A plain run (no --full) times the headline only -- no cpu_baseline, no secondary legs -- and --dump-outputs writes, as float64
+    DIR/<name>.npy, exactly the arrays the caller received for the instances of the last timed step."""
+    K, B, steps, maxit = 6, 3, 2, 3
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    dump, outdir = str(tmp_path / "rows.npy"), str(tmp_path / "outputs")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--backend", "gloo",
+           "--library", emu_lib, "--K", str(K), "--batch", str(B), "--max-iterations", str(maxit), "--dump", dump, "--dump-outputs", outdir]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and "cpu_baseline" not in d
+    assert not {"what_converged_means", "single_pool", "single_batch", "sc_mode", "mpc_mode", "other_instantiations"} & set(d["config"])
+    got = scpp_amd.Context.unpack_stream_rows(np.load(dump), K)
+    names = sorted(f[:-4] for f in os.listdir(outdir))
+    assert names == sorted(got)
+    for name in names:
+        a = np.load(os.path.join(outdir, name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, got[name][(steps - 1) * B:].astype(np.float64)), name
+    assert (np.load(os.path.join(outdir, "instance.npy")) == np.arange((steps - 1) * B, steps * B)).all()
+
+
+def test_bench_dump_outputs_samples_a_large_step(tmp_path, monkeypatch):
+    """Beyond the byte budget --dump-outputs keeps a seeded sample of the step's instances: the same sample on every call."""
+    import bench
+
+    n, lo = 40, 8
+    out = {"X": np.arange(n * 6, dtype=np.float64).reshape(n, 3, 2), "instance": np.arange(n, dtype=np.int32)}
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 10 * 7 * 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(out, lo, n, str(tmp_path / d))
+    ia, ib = (np.load(str(tmp_path / d / "instance.npy")) for d in ("a", "b"))
+    assert ia.dtype == np.float64 and ia.size == 10 and np.array_equal(ia, ib) and (np.diff(ia) > 0).all() and ia.min() >= lo
+    assert np.array_equal(np.load(str(tmp_path / "a" / "X.npy")), out["X"][ia.astype(int)])
+
+
 def test_bench_line_contract(emu_lib):
     """The ONE JSON line the driver parses: every key of the bench contract with the right type, the metric of BASELINE.json, the roofline and
     cpu_baseline objects, weak scaling, value = converged / time."""
@@ -142,7 +180,7 @@ def test_bench_line_contract(emu_lib):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--library", emu_lib,
-           "--K", "6", "--batch", "2", "--max-iterations", "3", "--no-extras"]  # (cpu_baseline bounds itself: ~12 s per solver)
+           "--K", "6", "--batch", "2", "--max-iterations", "3", "--full", "--no-extras"]  # (cpu_baseline bounds itself: ~12 s per solver)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@
 TAG=${1:-final}; ROOT=$PWD; OUT=$ROOT/gpurun_out/r02_$TAG; mkdir -p $OUT
 timeout -k 5 900 python -m pytest tests -m gpu -x -q -s > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/smoke.log
-timeout -k 5 900 python bench.py > $OUT/bench_default.log 2>&1; echo "bench default rc=$?"
+timeout -k 5 900 python bench.py --full > $OUT/bench_default.log 2>&1; echo "bench default rc=$?"
 grep '^{' $OUT/bench_default.log | tail -1 > $OUT/bench_default.json
 timeout -k 5 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_driver.log 2>&1; echo "bench driver-style rc=$?"
 grep '^{' $OUT/bench_driver.log | tail -1 > $OUT/bench_driver.json

@@ -2,7 +2,7 @@
 # round-2 GPU session 1: parity tests, the default bench line, slot-pool sweep, kernel-trace statistics
 ROOT=$PWD; OUT=$ROOT/gpurun_out/r02a; mkdir -p $OUT
 timeout -k 5 600 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
-timeout -k 5 600 python bench.py > $OUT/bench_default.log 2>&1; echo "bench rc=$?"
+timeout -k 5 600 python bench.py --full > $OUT/bench_default.log 2>&1; echo "bench rc=$?"
 grep '^{' $OUT/bench_default.log | tail -1 > $OUT/bench_default.json
 for P in 1 2 4; do
   timeout -k 5 300 python bench.py --pools $P --steps 3 --warmup 1 --no-extras --no-cpu-baseline > $OUT/bench_pools$P.log 2>&1

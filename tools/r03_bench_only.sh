@@ -2,7 +2,7 @@
 # official bench lines of the round-3 final library (default pools heuristic = 3 pools at 8192 slots)
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 O=gpurun_out/${OUTDIR:-r03_v2}; mkdir -p $O
-timeout -k 5 900 python bench.py > $O/bench_default.log 2>&1; echo "bench default rc=$?"
+timeout -k 5 900 python bench.py --full > $O/bench_default.log 2>&1; echo "bench default rc=$?"
 grep '^{' $O/bench_default.log | tail -1 > $O/bench_default.json
 timeout -k 5 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_driver.log 2>&1; echo "bench driver-style rc=$?"
 grep '^{' $O/bench_driver.log | tail -1 > $O/bench_driver.json

@@ -7,7 +7,7 @@ TAG=${1:-final}; ROOT=$PWD; OUT=$ROOT/gpurun_out/r03_$TAG; mkdir -p $OUT
 export GRAFT_COMMIT=$(cat tools/commit_id.txt 2>/dev/null || echo worktree)
 timeout -k 5 1500 python -m pytest tests -m gpu -q -s > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -3 $OUT/smoke.log
-timeout -k 5 900 python bench.py > $OUT/bench_default.log 2>&1; echo "bench default rc=$?"
+timeout -k 5 900 python bench.py --full > $OUT/bench_default.log 2>&1; echo "bench default rc=$?"
 grep '^{' $OUT/bench_default.log | tail -1 > $OUT/bench_default.json
 timeout -k 5 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_driver.log 2>&1; echo "bench driver-style rc=$?"
 grep '^{' $OUT/bench_driver.log | tail -1 > $OUT/bench_driver.json

@@ -2,7 +2,7 @@
 # round-5 session 20: the driver's exact bench command (extras and cpu_baseline included), and --gpus 2 on a one-GPU box (must refuse loudly)
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 O=gpurun_out/r05_s20; mkdir -p $O
-( time python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_exact.log 2> $O/bench_driver_exact.err ) 2> $O/time.txt; echo "driver-exact rc=$?"; grep real $O/time.txt
+( time python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_exact.log 2> $O/bench_driver_exact.err ) 2> $O/time.txt; echo "driver-exact rc=$?"; grep real $O/time.txt
 grep '^{' $O/bench_driver_exact.log | tail -1 > $O/bench_driver_exact.json
 python3 bench.py --gpus 2 --steps 1 --warmup 0 > $O/gpus2.out 2> $O/gpus2.err; echo "--gpus 2 on this box: rc=$? stdout bytes $(wc -c < $O/gpus2.out)"; tail -1 $O/gpus2.err
 python - <<PY

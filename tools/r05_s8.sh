@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 O=gpurun_out/r05_s8; mkdir -p $O
 timeout -k 5 2400 python -m pytest tests -m gpu -q -s -x > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -5 $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -3 $O/smoke.log
-timeout -k 5 900 python bench.py > $O/bench_default.log 2>&1; echo "bench default rc=$?"
+timeout -k 5 900 python bench.py --full > $O/bench_default.log 2>&1; echo "bench default rc=$?"
 grep '^{' $O/bench_default.log | tail -1 > $O/bench_default.json
 python - <<PY
 import json

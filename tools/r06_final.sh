@@ -27,7 +27,7 @@ bash tools/pmc_hbm.sh r06_$TAG 8192 2 > $OUT/pmc.log 2>&1
 cp gpurun_out/pmc_r06_$TAG/summary.json $OUT/pmc_summary.json
 # the bench lines LAST, with this session's PMC summary in place (same kernel-source hash -> not stale)
 cp $OUT/pmc_summary.json profiles/r06_pmc_hbm_v9_session.json
-timeout -k 5 900 python bench.py > $OUT/bench_default.log 2>&1; echo "bench default rc=$?"
+timeout -k 5 900 python bench.py --full > $OUT/bench_default.log 2>&1; echo "bench default rc=$?"
 grep '^{' $OUT/bench_default.log | tail -1 > $OUT/bench_default.json
 timeout -k 5 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_driver.log 2>&1; echo "bench driver-style rc=$?"
 grep '^{' $OUT/bench_driver.log | tail -1 > $OUT/bench_driver.json
