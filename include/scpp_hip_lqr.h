@@ -1,0 +1,99 @@
+/* scpp_hip_lqr.h -- C ABI of the batched LQR trajectory tracker (libscpp_lqr.so; gfx950).
+ *
+ * A component of its own next to scpp_hip.h: it uses the solver only through what the solver hands out (trajectories in SI units as
+ * scpp_hip_download / scpp_hip_stream_download return them, or the device pointers of scpp_hip_device_ptrs) and shares no state with it.
+ *
+ * What each entry point replaces in the reference:
+ *   LQRTracker::LQRTracker                scpp_core/src/LQRTracker.cpp:6-28       scpp_hip_lqr_compute_gains
+ *       ComputeLQR / careSolve / solveSchurIterative   scpp_core/src/LQR.cpp:7-109
+ *   LQRTracker::loadParameters            scpp_core/src/LQRTracker.cpp:30-41      scpp_hip_lqr_set_weights (the caller reads LQR.info)
+ *   LQRTracker::getInput, interpolateGains  LQRTracker.cpp:43-65, trajectoryData.hpp:41-78
+ *   the closed loop of SC_tracking        scpp/src/SC_tracking.cpp:48-75          scpp_hip_lqr_track
+ *       scpp::simulate (RKF78, fixed steps)   scpp_core/src/simulation.cpp:25-42
+ *   LQRAlgorithm::initialize / solve, the loop of LQR_sim   LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82   the same, see scpp_hip_lqr_set_stop_tolerance
+ *       (without LQR_sim's input clipping, which addresses u.z() of a two-input model and does not compile for Rocket2D)
+ *
+ * Deviations, all deliberate:
+ *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
+ *     is exactly singular wherever w_B = 0.
+ *   - zero-order hold: node k linearises at U[min(k, K-2)]; the reference special-cases k == K-2 and reads U.at(K-1) out of range at k = K-1.
+ *   - the node index is clamped to K-2 where t / dt rounds up to K-1 just below the flight time (the reference reads X.at(K)).
+ *   - a loop whose state or input goes non-finite (a non-finite reference node included) retires with status -2 and keeps its last
+ *     finite state and input (the reference throws); the errors are norms in double (the reference
+ *     truncates them to size_t).
+ *   - the record keeps every write_steps-th step.
+ *
+ * Conventions as in scpp_hip.h: every function returns 0 or a negative SCPP_E_* code, nothing throws; host buffers are caller-owned, float64
+ * (int32 where said), C-contiguous; one host thread per context.  All work goes on the context's own stream; nothing synchronises the device.
+ */
+#ifndef SCPP_HIP_LQR_H
+#define SCPP_HIP_LQR_H
+
+#ifdef __cplusplus
+extern "C"
+{
+#endif
+
+#ifndef SCPP_OK
+#define SCPP_OK 0
+#define SCPP_E_ARG -1
+#define SCPP_E_HIP -2
+#define SCPP_E_UNSUPPORTED -3
+#define SCPP_E_STATE -4
+#endif
+
+/* per-node gain status and per-instance tracking status */
+#define SCPP_LQR_OK 0
+#define SCPP_LQR_STEP_CAP 1         /* tracking: stopped by max_steps before the flight time */
+#define SCPP_LQR_ITERATION_LIMIT -1 /* gains: 101 sign iterations without convergence (LQR.cpp:19-20) */
+#define SCPP_LQR_NONFINITE -2       /* gains: singular or non-finite Hamiltonian; tracking: non-finite state */
+
+    typedef struct scpp_hip_lqr_ctx scpp_hip_lqr_ctx;
+
+    const char *scpp_hip_lqr_version(void);
+    /* model_id as in scpp_hip.h (0 RocketQuat, 1 Rocket2D, 2 Lander3dof); K >= 2 nodes; foh != 0: U [B][K][nu], else U [B][K-1][nu].
+       Weights start as Q = I, R = I.  SCPP_E_ARG for an unknown model, K < 2, batch_max < 1. */
+    int scpp_hip_lqr_create(scpp_hip_lqr_ctx **ctx, int device_id, int model_id, int K, int batch_max, int foh);
+    int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *ctx);
+    int scpp_hip_lqr_dims(scpp_hip_lqr_ctx *ctx, int *nx, int *nu, int *np, int *nr /* order of the Riccati equation */);
+    /* diagonals of Q and R (LQR.info: state_weights, input_weights); every entry must be finite and > 0, else SCPP_E_ARG */
+    int scpp_hip_lqr_set_weights(scpp_hip_lqr_ctx *ctx, const double *q /* [nx] */, const double *r /* [nu] */);
+    /* flow-map parameters in SI units (flow_params(nondimensionalize=False)); B == 1 broadcasts one row to every instance, otherwise B must
+       equal the number of trajectories: scpp_hip_lqr_compute_gains / _track return SCPP_E_STATE when it does not */
+    int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *ctx, const double *par /* [B][np] */, int B);
+    /* trajectories in SI units: X [B][K][nx], U [B][K or K-1][nu], flight time t [B]; invalidates gains */
+    int scpp_hip_lqr_set_trajectories(scpp_hip_lqr_ctx *ctx, const double *X, const double *U, const double *t, int B);
+    /* the same from device memory: not copied, the caller keeps the buffers alive and orders its own stream before the next call here.
+       u_rows is the row stride of dU per trajectory, dU [B][u_rows][nu] with u_rows >= the K or K-1 inputs of this context (SCPP_E_ARG
+       otherwise).  scpp_hip_device_ptrs of a solved context hands out the redimensionalised result buffers X [B][K][nx], U [B][K][nu]
+       (K rows whatever the hold: pass u_rows = K, a zero-order-hold tracker then skips the unused last row) and sigma [B]. */
+    int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *ctx, const void *dX, const void *dU, const void *dt, int B, int u_rows);
+    /* one gain per (instance, node); *n_ok (optional) = nodes with status 0.  SCPP_E_STATE without trajectories or flow parameters. */
+    int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *ctx, int *n_ok);
+    /* gains [B][K][nu][nx], status [B][K] int32, iters [B][K] int32 (sign iterations); any pointer may be NULL */
+    int scpp_hip_lqr_download_gains(scpp_hip_lqr_ctx *ctx, double *gains, int *status, int *iters);
+    /* user-supplied gains [B][K][nu][nx] for the trajectories set before; non-finite entries are refused (SCPP_E_ARG) */
+    int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *ctx, const double *gains);
+    /* regulator mode (LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82): with stop_tol > 0 a loop also ends once |x - x_final| < stop_tol.  The
+       caller sets a constant two-node "trajectory" (X = x_final, U = u_eq, t = sim_time) and the one gain of the operating point
+       (scpp_hip_lqr_set_gains), so that u = -K (x - x_final) + u_eq; the same two kernels, no third.  0 (the default) switches it off. */
+    int scpp_hip_lqr_set_stop_tolerance(scpp_hip_lqr_ctx *ctx, double stop_tol);
+    /* B closed loops from x_start [B][nx] towards x_final [nx] along the trajectories: time_step > 0 (reference: 0.01), substeps >= 1 RKF78
+       steps per plant step (reference: 20), at most max_steps >= 1 plant steps; the first n_record instances record every write_steps-th
+       step.  *n_finite (optional) = loops that did not retire non-finite. */
+    int scpp_hip_lqr_track(scpp_hip_lqr_ctx *ctx, const double *x_start, const double *x_final, int B, double time_step, int substeps,
+                           int max_steps, int n_record, int write_steps, int *n_finite);
+    /* x [B][nx], u [B][nu] (last input), t [B], steps [B] int32, status [B] int32, err0 / err1 [B] = |x - x_final| at start / end,
+       max_dev [B] = largest |x - x_ref| met; any pointer may be NULL */
+    int scpp_hip_lqr_track_download(scpp_hip_lqr_ctx *ctx, double *x, double *u, double *t, int *steps, int *status, double *err0,
+                                    double *err1, double *max_dev);
+    /* rows of the record of the last scpp_hip_lqr_track: *n_record, *rec_cap = ceil(max_steps / write_steps) */
+    int scpp_hip_lqr_track_record_size(scpp_hip_lqr_ctx *ctx, int *n_record, int *rec_cap);
+    /* X [n_record][rec_cap][nx], U [n_record][rec_cap][nu], t [n_record][rec_cap], n [n_record] int32 = rows written per instance */
+    int scpp_hip_lqr_track_record(scpp_hip_lqr_ctx *ctx, double *X, double *U, double *t, int *n);
+    int scpp_hip_lqr_synchronize(scpp_hip_lqr_ctx *ctx);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

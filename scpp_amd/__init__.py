@@ -26,3 +26,5 @@ from .sc_sim import SCSim, interpolated_input  # noqa: F401
 from .scvx_algorithm import SCvxAlgorithm, load_scvx_opts  # noqa: F401
 from .mpc_algorithm import MPCAlgorithm, MPCSim  # noqa: F401
 from ._lib import MpcOpts  # noqa: F401
+from ._lib import LqrContext, load_lqr_library  # noqa: F401
+from .lqr import LQRAlgorithm, LQRSim, LQRTracker, load_lqr_weights  # noqa: F401

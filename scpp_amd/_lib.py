@@ -472,3 +472,134 @@ class Context:
 
     def synchronize(self):
         _chk(self.lib.scpp_hip_synchronize(self.h), "synchronize")
+
+
+# ---- the LQR tracker: a library of its own (include/scpp_hip_lqr.h, csrc/lqr/), bound separately ----
+LQR_OK, LQR_STEP_CAP, LQR_ITERATION_LIMIT, LQR_NONFINITE = 0, 1, -1, -2
+LQR_SYMBOLS = [
+    "scpp_hip_lqr_version", "scpp_hip_lqr_create", "scpp_hip_lqr_destroy", "scpp_hip_lqr_dims", "scpp_hip_lqr_set_weights",
+    "scpp_hip_lqr_set_flow_params", "scpp_hip_lqr_set_trajectories", "scpp_hip_lqr_set_trajectories_device", "scpp_hip_lqr_compute_gains",
+    "scpp_hip_lqr_download_gains", "scpp_hip_lqr_set_gains", "scpp_hip_lqr_set_stop_tolerance", "scpp_hip_lqr_track", "scpp_hip_lqr_track_download",
+    "scpp_hip_lqr_track_record_size", "scpp_hip_lqr_track_record", "scpp_hip_lqr_synchronize",
+]
+_lqr_libs = {}
+
+
+def load_lqr_library(path=None):
+    """Load libscpp_lqr.so (built by __graft_entry__.build()).  Raises ScppHipError if it is missing: no CPU fallback.  Tests pass the
+    path of the emulation build (tests/emu/libscpp_lqr_emu.so) explicitly."""
+    if path is None:
+        path = os.environ.get("SCPP_LQR_LIBRARY", os.path.join(_HERE, "libscpp_lqr.so"))
+    if path in _lqr_libs:
+        return _lqr_libs[path]
+    if not os.path.exists(path):
+        raise ScppHipError(
+            f"{path} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
+            "scpp_amd has no CPU fallback."
+        )
+    lib = C.CDLL(path)
+    for s in LQR_SYMBOLS:
+        if not hasattr(lib, s):
+            raise ScppHipError(f"{path} does not export {s}")
+    lib.scpp_hip_lqr_version.restype = C.c_char_p
+    lib.scpp_hip_lqr_track.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.scpp_hip_lqr_set_trajectories_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    _lqr_libs[path] = lib
+    return lib
+
+
+class LqrContext:
+    """One scpp_hip_lqr_ctx (one GPU, one stream): gains and closed loops for up to batch_max trajectories of K nodes."""
+
+    def __init__(self, model=MODEL_ROCKETQUAT, K=50, batch_max=1, foh=True, device=0, library=None):
+        self.lib = load_lqr_library(library)
+        self.model, self.K, self.batch_max, self.foh = int(model), int(K), int(batch_max), bool(foh)
+        h = C.c_void_p()
+        _chk(self.lib.scpp_hip_lqr_create(C.byref(h), int(device), int(model), int(K), int(batch_max), int(bool(foh))), "scpp_hip_lqr_create")
+        self.h = h
+        d = [C.c_int() for _ in range(4)]
+        _chk(self.lib.scpp_hip_lqr_dims(self.h, *[C.byref(v) for v in d]), "lqr_dims")
+        self.nx, self.nu, self.np_, self.nr = (int(v.value) for v in d)
+        self.nU = self.K if self.foh else self.K - 1
+        self.B = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.scpp_hip_lqr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, q, r):
+        q = np.ascontiguousarray(q, dtype=np.float64).reshape(self.nx)
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(self.nu)
+        _chk(self.lib.scpp_hip_lqr_set_weights(self.h, _p(q), _p(r)), "lqr_set_weights")
+
+    def set_flow_params(self, par):
+        par = np.ascontiguousarray(par, dtype=np.float64).reshape(-1, self.np_)
+        _chk(self.lib.scpp_hip_lqr_set_flow_params(self.h, _p(par), int(par.shape[0])), "lqr_set_flow_params")
+
+    def set_trajectories(self, X, U, t):
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, self.K, self.nx)
+        U = np.ascontiguousarray(U, dtype=np.float64).reshape(X.shape[0], self.nU, self.nu)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(X.shape[0])
+        _chk(self.lib.scpp_hip_lqr_set_trajectories(self.h, _p(X), _p(U), _p(t), int(X.shape[0])), "lqr_set_trajectories")
+        self.B = X.shape[0]
+
+    def set_trajectories_device(self, dX, dU, dt, B, u_rows=None):
+        """device pointers (integers), e.g. Context.device_ptrs() of a solved context (u_rows = K, the default): not copied"""
+        u_rows = self.K if u_rows is None else u_rows
+        _chk(self.lib.scpp_hip_lqr_set_trajectories_device(self.h, C.c_void_p(dX), C.c_void_p(dU), C.c_void_p(dt), int(B), int(u_rows)),
+             "lqr_set_trajectories_device")
+        self.B = int(B)
+
+    def compute_gains(self):
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_compute_gains(self.h, C.byref(n)), "lqr_compute_gains")
+        return int(n.value)
+
+    def download_gains(self, with_status=True):
+        G = np.zeros((self.B, self.K, self.nu, self.nx))
+        st = np.zeros((self.B, self.K), dtype=np.int32) if with_status else None
+        it = np.zeros((self.B, self.K), dtype=np.int32) if with_status else None
+        _chk(self.lib.scpp_hip_lqr_download_gains(self.h, _p(G), _p(st), _p(it)), "lqr_download_gains")
+        return dict(gains=G, status=st, iters=it) if with_status else dict(gains=G)
+
+    def set_gains(self, G):
+        G = np.ascontiguousarray(G, dtype=np.float64).reshape(self.B, self.K, self.nu, self.nx)
+        _chk(self.lib.scpp_hip_lqr_set_gains(self.h, _p(G)), "lqr_set_gains")
+
+    def set_stop_tolerance(self, stop_tol):
+        _chk(self.lib.scpp_hip_lqr_set_stop_tolerance(self.h, C.c_double(stop_tol)), "lqr_set_stop_tolerance")
+
+    def track(self, x_start, x_final, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30):
+        x_start = np.ascontiguousarray(x_start, dtype=np.float64).reshape(-1, self.nx)
+        x_final = np.ascontiguousarray(x_final, dtype=np.float64).reshape(self.nx)
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_track(self.h, _p(x_start), _p(x_final), int(x_start.shape[0]), float(time_step), int(substeps),
+                                         int(max_steps), int(n_record), int(write_steps), C.byref(n)), "lqr_track")
+        self.track_B = x_start.shape[0]
+        return int(n.value)
+
+    def track_download(self):
+        B = self.track_B
+        out = dict(x=np.zeros((B, self.nx)), u=np.zeros((B, self.nu)), t=np.zeros(B), steps=np.zeros(B, dtype=np.int32),
+                   status=np.zeros(B, dtype=np.int32), err0=np.zeros(B), err1=np.zeros(B), max_dev=np.zeros(B))
+        _chk(self.lib.scpp_hip_lqr_track_download(self.h, *[_p(out[k]) for k in ("x", "u", "t", "steps", "status", "err0", "err1", "max_dev")]),
+             "lqr_track_download")
+        return out
+
+    def track_record(self):
+        nr, cap = C.c_int(), C.c_int()
+        _chk(self.lib.scpp_hip_lqr_track_record_size(self.h, C.byref(nr), C.byref(cap)), "lqr_track_record_size")
+        nr, cap = int(nr.value), int(cap.value)
+        X, U, t, n = np.zeros((nr, cap, self.nx)), np.zeros((nr, cap, self.nu)), np.zeros((nr, cap)), np.zeros(nr, dtype=np.int32)
+        _chk(self.lib.scpp_hip_lqr_track_record(self.h, _p(X), _p(U), _p(t), _p(n)), "lqr_track_record")
+        return dict(X=X, U=U, t=t, n=n)
+
+    def synchronize(self):
+        _chk(self.lib.scpp_hip_lqr_synchronize(self.h), "lqr_synchronize")

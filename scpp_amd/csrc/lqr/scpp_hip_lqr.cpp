@@ -1,0 +1,512 @@
+// C ABI of the batched LQR tracker (include/scpp_hip_lqr.h): context, buffers and launches for csrc/lqr/lqr_kernels.h.
+// Built as a library of its own (libscpp_lqr.so; with -DSCPP_HIP_EMU: the CPU emulation of the same source), see DESIGN.md 4.8.
+#include "../../../include/scpp_hip_lqr.h"
+#include "lqr_kernels.h"
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+using namespace scpp;
+using namespace scpp::lqr;
+
+#define CHECK_HIP(expr)        \
+    do                         \
+    {                          \
+        if ((expr) != hipSuccess) \
+            return SCPP_E_HIP; \
+    } while (0)
+
+// f(Plugin{}) for the plugin whose ID is `model`; SCPP_E_ARG for an id nobody registered
+template <class F, class... PL>
+static int withLqrPluginOf(LqrPluginList<PL...>, int model, F &&f)
+{
+    int rc = SCPP_E_ARG;
+    (void)((model == PL::ID ? (rc = f(PL{}), true) : false) || ...);
+    return rc;
+}
+template <class F>
+static int withLqrPlugin(int model, F &&f)
+{
+    return withLqrPluginOf(LqrPlugins{}, model, std::forward<F>(f));
+}
+
+struct scpp_hip_lqr_ctx
+{
+    int device = 0, model = 0, K = 0, nU = 0, uRows = 0, Bmax = 0, B = 0;
+    int par_rows = 0; // rows given to scpp_hip_lqr_set_flow_params: 1 (shared) or the number of trajectories
+    int nx = 0, nu = 0, np = 0, nr = 0;
+    hipStream_t stream = nullptr;
+    double *X = nullptr, *U = nullptr, *T = nullptr;          // owned copies (scpp_hip_lqr_set_trajectories)
+    const double *tX = nullptr, *tU = nullptr, *tT = nullptr; // the trajectories in use: the owned copies or the caller's device memory
+    double *par = nullptr, *q = nullptr, *r = nullptr, *G = nullptr;
+    int *gstatus = nullptr, *giters = nullptr;
+    double *xs = nullptr, *xf = nullptr, *ox = nullptr, *ou = nullptr, *os = nullptr;
+    int *oi = nullptr;
+    double *rx = nullptr, *ru = nullptr, *rt = nullptr;
+    int *rn = nullptr;
+    int n_record = 0, rec_cap = 0, rec_alloc_rows = 0, rec_alloc_inst = 0;
+    int par_stride = 0;
+    bool have_par = false, have_traj = false, have_gains = false, gains_computed = false, have_track = false;
+    int track_B = 0;
+    double stop_tol = 0.;
+};
+
+template <class T>
+static int devAlloc(T **p, size_t n)
+{
+    return hipMalloc(reinterpret_cast<void **>(p), (n ? n : 1) * sizeof(T)) == hipSuccess ? 0 : 1;
+}
+
+struct DeviceGuard
+{
+    int prev = -1;
+    explicit DeviceGuard(int want)
+    {
+        (void)hipGetDevice(&prev);
+        if (prev == want)
+            prev = -1;
+        else
+            (void)hipSetDevice(want);
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0)
+            (void)hipSetDevice(prev);
+    }
+};
+
+// host staging memory that cannot throw across the C ABI: a failed allocation is reported as SCPP_E_HIP by the caller
+template <class T>
+struct HostBuf
+{
+    T *p;
+    size_t n;
+    explicit HostBuf(size_t n_) : p(static_cast<T *>(std::malloc((n_ ? n_ : 1) * sizeof(T)))), n(n_) {}
+    ~HostBuf() { std::free(p); }
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+};
+
+static bool allFinite(const double *v, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(v[i]))
+            return false;
+    return true;
+}
+
+extern "C"
+{
+
+const char *scpp_hip_lqr_version(void)
+{
+#ifdef SCPP_HIP_EMU
+    return "scpp_hip_lqr 1 (cpu emulation)";
+#else
+    return "scpp_hip_lqr 1 (gfx950)";
+#endif
+}
+
+int scpp_hip_lqr_create(scpp_hip_lqr_ctx **out, int device_id, int model_id, int K, int batch_max, int foh)
+{
+    if (!out || K < 2 || batch_max < 1)
+        return SCPP_E_ARG;
+    *out = nullptr;
+    if (withLqrPlugin(model_id, [](auto) { return 0; }) != 0)
+        return SCPP_E_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev)
+        return SCPP_E_HIP;
+    DeviceGuard guard(device_id);
+    scpp_hip_lqr_ctx *c = new (std::nothrow) scpp_hip_lqr_ctx;
+    if (!c)
+        return SCPP_E_HIP;
+    c->device = device_id;
+    c->model = model_id;
+    c->K = K;
+    c->nU = foh ? K : K - 1;
+    c->Bmax = batch_max;
+    (void)withLqrPlugin(model_id, [&](auto pl) {
+        using P = decltype(pl);
+        c->nx = P::Model::NX;
+        c->nu = P::Model::NU;
+        c->np = P::Model::NP;
+        c->nr = P::NR;
+        return 0;
+    });
+    if (hipStreamCreate(&c->stream) != hipSuccess)
+    {
+        delete c;
+        return SCPP_E_HIP;
+    }
+    const size_t B = size_t(batch_max), nx = size_t(c->nx), nu = size_t(c->nu);
+    int rc = 0;
+    rc |= devAlloc(&c->X, B * K * nx);
+    rc |= devAlloc(&c->U, B * c->nU * nu);
+    rc |= devAlloc(&c->T, B);
+    rc |= devAlloc(&c->par, B * c->np);
+    rc |= devAlloc(&c->q, nx);
+    rc |= devAlloc(&c->r, nu);
+    rc |= devAlloc(&c->G, B * K * nu * nx);
+    rc |= devAlloc(&c->gstatus, B * K);
+    rc |= devAlloc(&c->giters, B * K);
+    rc |= devAlloc(&c->xs, B * nx);
+    rc |= devAlloc(&c->xf, nx);
+    rc |= devAlloc(&c->ox, B * nx);
+    rc |= devAlloc(&c->ou, B * nu);
+    rc |= devAlloc(&c->os, B * 4);
+    rc |= devAlloc(&c->oi, B * 2);
+    if (rc == 0)
+    {
+        HostBuf<double> one(nx > nu ? nx : nu);
+        rc |= one.p == nullptr;
+        for (size_t i = 0; one.p && i < one.n; i++)
+            one.p[i] = 1.;
+        rc |= rc || hipMemcpy(c->q, one.p, nx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess;
+        rc |= rc || hipMemcpy(c->r, one.p, nu * sizeof(double), hipMemcpyHostToDevice) != hipSuccess;
+    }
+    if (rc)
+    {
+        scpp_hip_lqr_destroy(c);
+        return SCPP_E_HIP;
+    }
+    *out = c;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    if (c->stream)
+        (void)hipStreamSynchronize(c->stream);
+    void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn};
+    for (void *p : bufs)
+        if (p)
+            (void)hipFree(p);
+    if (c->stream)
+        (void)hipStreamDestroy(c->stream);
+    delete c;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_dims(scpp_hip_lqr_ctx *c, int *nx, int *nu, int *np, int *nr)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (nx)
+        *nx = c->nx;
+    if (nu)
+        *nu = c->nu;
+    if (np)
+        *np = c->np;
+    if (nr)
+        *nr = c->nr;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_weights(scpp_hip_lqr_ctx *c, const double *q, const double *r)
+{
+    if (!c || !q || !r)
+        return SCPP_E_ARG;
+    for (int i = 0; i < c->nx; i++)
+        if (!std::isfinite(q[i]) || !(q[i] > 0.))
+            return SCPP_E_ARG;
+    for (int i = 0; i < c->nu; i++)
+        if (!std::isfinite(r[i]) || !(r[i] > 0.))
+            return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    CHECK_HIP(hipMemcpyAsync(c->q, q, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipMemcpyAsync(c->r, r, size_t(c->nu) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
+    if (c->gains_computed)
+        c->have_gains = c->gains_computed = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
+{
+    if (!c || !par || B < 1 || B > c->Bmax)
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    CHECK_HIP(hipMemcpyAsync(c->par, par, size_t(B) * c->np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    c->par_stride = (B == 1) ? 0 : c->np;
+    c->par_rows = B;
+    c->have_par = true;
+    if (c->gains_computed)
+        c->have_gains = c->gains_computed = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_trajectories(scpp_hip_lqr_ctx *c, const double *X, const double *U, const double *t, int B)
+{
+    if (!c || !X || !U || !t || B < 1 || B > c->Bmax)
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    CHECK_HIP(hipMemcpyAsync(c->X, X, size_t(B) * c->K * c->nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipMemcpyAsync(c->U, U, size_t(B) * c->nU * c->nu * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipMemcpyAsync(c->T, t, size_t(B) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    c->tX = c->X;
+    c->tU = c->U;
+    c->tT = c->T;
+    c->uRows = c->nU;
+    c->B = B;
+    c->have_traj = true;
+    c->have_gains = c->gains_computed = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *c, const void *dX, const void *dU, const void *dt, int B, int u_rows)
+{
+    if (!c || !dX || !dU || !dt || B < 1 || B > c->Bmax || u_rows < c->nU)
+        return SCPP_E_ARG;
+    c->tX = static_cast<const double *>(dX);
+    c->tU = static_cast<const double *>(dU);
+    c->tT = static_cast<const double *>(dt);
+    c->uRows = u_rows;
+    c->B = B;
+    c->have_traj = true;
+    c->have_gains = c->gains_computed = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_traj || !c->have_par)
+        return SCPP_E_STATE;
+    if (c->par_rows != 1 && c->par_rows != c->B)
+        return SCPP_E_STATE; // parameter rows for another number of trajectories
+    DeviceGuard guard(c->device);
+    const long nodes = long(c->B) * c->K;
+    const unsigned grid = unsigned((nodes + 1) / 2);
+    int rc = withLqrPlugin(c->model, [&](auto pl) {
+        using P = decltype(pl);
+        hipLaunchKernelGGL((lqr_gain_kernel<P>), dim3(grid), dim3(WAVE), 0, c->stream, nodes, c->K, c->nU, c->uRows, c->tX, c->tU,
+                           (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r, c->G, c->gstatus, c->giters);
+        return 0;
+    });
+    if (rc)
+        return rc;
+    if (hipGetLastError() != hipSuccess)
+        return SCPP_E_HIP;
+    c->have_gains = c->gains_computed = true;
+    if (n_ok)
+    {
+        HostBuf<int> st(static_cast<size_t>(nodes));
+        if (!st.p)
+            return SCPP_E_HIP;
+        CHECK_HIP(hipMemcpyAsync(st.p, c->gstatus, size_t(nodes) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        int n = 0;
+        for (long i = 0; i < nodes; i++)
+            n += (st.p[i] == SCPP_LQR_OK);
+        *n_ok = n;
+    }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_download_gains(scpp_hip_lqr_ctx *c, double *gains, int *status, int *iters)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_gains)
+        return SCPP_E_STATE;
+    if ((status || iters) && !c->gains_computed)
+        return SCPP_E_STATE; // user-supplied gains carry no status
+    DeviceGuard guard(c->device);
+    const size_t nodes = size_t(c->B) * c->K;
+    if (gains)
+        CHECK_HIP(hipMemcpyAsync(gains, c->G, nodes * c->nu * c->nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (status)
+        CHECK_HIP(hipMemcpyAsync(status, c->gstatus, nodes * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (iters)
+        CHECK_HIP(hipMemcpyAsync(iters, c->giters, nodes * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *c, const double *gains)
+{
+    if (!c || !gains)
+        return SCPP_E_ARG;
+    if (!c->have_traj)
+        return SCPP_E_STATE;
+    const size_t n = size_t(c->B) * c->K * c->nu * c->nx;
+    if (!allFinite(gains, n))
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    CHECK_HIP(hipMemcpyAsync(c->G, gains, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    c->have_gains = true;
+    c->gains_computed = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_stop_tolerance(scpp_hip_lqr_ctx *c, double stop_tol)
+{
+    if (!c || !(stop_tol >= 0.) || !std::isfinite(stop_tol))
+        return SCPP_E_ARG;
+    c->stop_tol = stop_tol;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_track(scpp_hip_lqr_ctx *c, const double *x_start, const double *x_final, int B, double time_step, int substeps, int max_steps,
+                       int n_record, int write_steps, int *n_finite)
+{
+    if (!c || !x_start || !x_final || B < 1 || !(time_step > 0.) || !std::isfinite(time_step) || substeps < 1 || max_steps < 1 ||
+        n_record < 0 || n_record > B || (n_record > 0 && write_steps < 1))
+        return SCPP_E_ARG;
+    if (!c->have_traj || !c->have_par || !c->have_gains)
+        return SCPP_E_STATE;
+    if (c->par_rows != 1 && c->par_rows != c->B)
+        return SCPP_E_STATE;
+    if (B != c->B)
+        return SCPP_E_ARG; // one start per trajectory
+    if (!allFinite(x_final, size_t(c->nx)))
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    if (write_steps < 1)
+        write_steps = 1;
+    const int rec_cap = n_record > 0 ? (max_steps + write_steps - 1) / write_steps : 0;
+    if (n_record > 0 && (n_record > c->rec_alloc_inst || rec_cap > c->rec_alloc_rows))
+    {
+        // sized by n_record and the rows asked for, not by batch_max
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        void *old[] = {c->rx, c->ru, c->rt, c->rn};
+        for (void *p : old)
+            if (p)
+                (void)hipFree(p);
+        c->rx = c->ru = c->rt = nullptr;
+        c->rn = nullptr;
+        c->rec_alloc_inst = c->rec_alloc_rows = 0;
+        const size_t rows = size_t(n_record) * rec_cap;
+        if (devAlloc(&c->rx, rows * c->nx) | devAlloc(&c->ru, rows * c->nu) | devAlloc(&c->rt, rows) | devAlloc(&c->rn, size_t(n_record)))
+            return SCPP_E_HIP;
+        c->rec_alloc_inst = n_record;
+        c->rec_alloc_rows = rec_cap;
+    }
+    CHECK_HIP(hipMemcpyAsync(c->xs, x_start, size_t(B) * c->nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipMemcpyAsync(c->xf, x_final, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const unsigned grid = unsigned((B + WAVE - 1) / WAVE);
+    int rc = withLqrPlugin(c->model, [&](auto pl) {
+        using P = decltype(pl);
+        hipLaunchKernelGGL((lqr_track_kernel<P>), dim3(grid), dim3(WAVE), 0, c->stream, B, c->K, c->nU, c->uRows, c->tX, c->tU, c->tT,
+                           (const double *)c->par, c->par_stride, (const double *)c->G, (const double *)c->xs, (const double *)c->xf, time_step,
+                           substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn);
+        return 0;
+    });
+    if (rc)
+        return rc;
+    if (hipGetLastError() != hipSuccess)
+        return SCPP_E_HIP;
+    CHECK_HIP(hipStreamSynchronize(c->stream)); // x_start / x_final are the caller's
+    c->have_track = true;
+    c->track_B = B;
+    c->n_record = n_record;
+    c->rec_cap = rec_cap;
+    if (n_finite)
+    {
+        HostBuf<int> oi(size_t(B) * 2);
+        if (!oi.p)
+            return SCPP_E_HIP;
+        CHECK_HIP(hipMemcpyAsync(oi.p, c->oi, oi.n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        int n = 0;
+        for (int b = 0; b < B; b++)
+            n += (oi.p[size_t(b) * 2 + 1] != SCPP_LQR_NONFINITE);
+        *n_finite = n;
+    }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_track_download(scpp_hip_lqr_ctx *c, double *x, double *u, double *t, int *steps, int *status, double *err0, double *err1,
+                                double *max_dev)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_track)
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t B = size_t(c->track_B);
+    HostBuf<double> osb(B * 4);
+    HostBuf<int> oib(B * 2);
+    if (!osb.p || !oib.p)
+        return SCPP_E_HIP;
+    double *os = osb.p;
+    int *oi = oib.p;
+    if (x)
+        CHECK_HIP(hipMemcpyAsync(x, c->ox, B * c->nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (u)
+        CHECK_HIP(hipMemcpyAsync(u, c->ou, B * c->nu * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipMemcpyAsync(os, c->os, osb.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipMemcpyAsync(oi, c->oi, oib.n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < B; b++)
+    {
+        if (t)
+            t[b] = os[b * 4 + 0];
+        if (err0)
+            err0[b] = os[b * 4 + 1];
+        if (err1)
+            err1[b] = os[b * 4 + 2];
+        if (max_dev)
+            max_dev[b] = os[b * 4 + 3];
+        if (steps)
+            steps[b] = oi[b * 2 + 0];
+        if (status)
+            status[b] = oi[b * 2 + 1];
+    }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_track_record_size(scpp_hip_lqr_ctx *c, int *n_record, int *rec_cap)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_track)
+        return SCPP_E_STATE;
+    if (n_record)
+        *n_record = c->n_record;
+    if (rec_cap)
+        *rec_cap = c->rec_cap;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_track_record(scpp_hip_lqr_ctx *c, double *X, double *U, double *t, int *n)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_track || c->n_record < 1)
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    // the kernel addresses the record with the row count of THIS call (rec_cap), whatever the allocation holds
+    const size_t rows = size_t(c->n_record) * c->rec_cap;
+    if (n)
+        CHECK_HIP(hipMemcpyAsync(n, c->rn, size_t(c->n_record) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (t)
+        CHECK_HIP(hipMemcpyAsync(t, c->rt, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (X)
+        CHECK_HIP(hipMemcpyAsync(X, c->rx, rows * c->nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (U)
+        CHECK_HIP(hipMemcpyAsync(U, c->ru, rows * c->nu * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_synchronize(scpp_hip_lqr_ctx *c)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,204 @@
+// C++17 host front end of the LQR tracker over include/scpp_hip_lqr.h: the reference's LQRTracker
+//   LQRTracker(model, td), getInput(t, x, u), interpolateGains(t)       scpp_core/include/LQRTracker.hpp, src/LQRTracker.cpp:6-65
+// for a batch of trajectories, plus the closed loop of scpp/src/SC_tracking.cpp:48-75 on the device (track).  The gains and the
+// flights are computed by libscpp_lqr.so; there is no CPU fallback.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <filesystem>
+#include <utility>
+
+#include "sc_algorithm.hpp"
+#include "scpp_hip_lqr.h"
+
+namespace scpp
+{
+
+struct lqr_track_result_t
+{
+    std::vector<Model::state_vector_t> x; // final states
+    std::vector<Model::input_vector_t> u; // last inputs
+    std::vector<double> t, initial_error, final_error, max_deviation;
+    std::vector<int32_t> steps, status;
+    int n_finite = 0;
+    // record of the first n_record flights, every write_steps-th step
+    std::vector<std::vector<Model::state_vector_t>> X_sim;
+    std::vector<std::vector<Model::input_vector_t>> U_sim;
+    std::vector<std::vector<double>> t_sim;
+};
+
+class LQRTracker
+{
+public:
+    static constexpr size_t NX = Model::state_dim, NU = Model::input_dim;
+    using feedback_matrix_t = std::array<std::array<double, NX>, NU>;
+
+    // LQRTracker.cpp:6-28 for every trajectory of `tds` (all with the same K and hold): the gains are computed here
+    // `weights`: (state_weights [NX], input_weights [NU]) instead of those of LQR.info
+    LQRTracker(Model::ptr_t model_, const std::vector<trajectory_data_t> &tds_, int device = 0,
+               const std::pair<std::array<double, NX>, std::array<double, NU>> *weights = nullptr)
+        : model(std::move(model_)), tds(tds_)
+    {
+        if (tds.empty() || tds[0].n_X() < 2)
+            throw std::invalid_argument("LQRTracker: at least one trajectory of at least two nodes");
+        const int B = int(tds.size()), K = int(tds[0].n_X());
+        const bool foh = tds[0].interpolatedInput();
+        const size_t nU = tds[0].n_U();
+        if (weights)
+        {
+            Q = weights->first;
+            R = weights->second;
+        }
+        else
+            loadParameters();
+        check(scpp_hip_lqr_create(&ctx, device, Model::model_id, K, B, foh ? 1 : 0), "scpp_hip_lqr_create");
+        check(scpp_hip_lqr_set_weights(ctx, Q.data(), R.data()), "scpp_hip_lqr_set_weights");
+        std::vector<double> par(Model::param_dim);
+        model->flowParams(par.data());
+        check(scpp_hip_lqr_set_flow_params(ctx, par.data(), 1), "scpp_hip_lqr_set_flow_params");
+        std::vector<double> X(size_t(B) * K * NX), U(size_t(B) * nU * NU), t(static_cast<size_t>(B), 0.);
+        for (int b = 0; b < B; b++)
+        {
+            const trajectory_data_t &td = tds[size_t(b)];
+            if (int(td.n_X()) != K || td.n_U() != nU)
+                throw std::invalid_argument("LQRTracker: trajectories of different shapes");
+            for (size_t k = 0; k < size_t(K); k++)
+                std::copy(td.X[k].begin(), td.X[k].end(), &X[(size_t(b) * K + k) * NX]);
+            for (size_t k = 0; k < nU; k++)
+                std::copy(td.U[k].begin(), td.U[k].end(), &U[(size_t(b) * nU + k) * NU]);
+            t[size_t(b)] = td.t;
+        }
+        check(scpp_hip_lqr_set_trajectories(ctx, X.data(), U.data(), t.data(), B), "scpp_hip_lqr_set_trajectories");
+        check(scpp_hip_lqr_compute_gains(ctx, &n_ok), "scpp_hip_lqr_compute_gains");
+        gains.resize(size_t(B) * K);
+        status.resize(size_t(B) * K);
+        iterations.resize(size_t(B) * K);
+        check(scpp_hip_lqr_download_gains(ctx, &gains[0][0][0], status.data(), iterations.data()), "scpp_hip_lqr_download_gains");
+    }
+    LQRTracker(Model::ptr_t model_, const trajectory_data_t &td, int device = 0,
+               const std::pair<std::array<double, NX>, std::array<double, NU>> *weights = nullptr)
+        : LQRTracker(std::move(model_), std::vector<trajectory_data_t>{td}, device, weights)
+    {
+    }
+    ~LQRTracker()
+    {
+        if (ctx)
+            scpp_hip_lqr_destroy(ctx);
+    }
+    LQRTracker(const LQRTracker &) = delete;
+    LQRTracker &operator=(const LQRTracker &) = delete;
+
+    // LQRTracker.cpp:30-41; Q = I, R = I without an LQR.info
+    void loadParameters()
+    {
+        Q.fill(1.);
+        R.fill(1.);
+        const std::string file = Model::getParameterFolder() + "/LQR.info";
+        if (!std::filesystem::exists(file))
+            return;
+        ParameterServer param(file);
+        param.loadMatrix("state_weights", Q.data(), int(NX));
+        param.loadMatrix("input_weights", R.data(), int(NU));
+    }
+
+    const feedback_matrix_t &gain(size_t b, size_t k) const { return gains[b * tds[0].n_X() + k]; }
+    int nodesConverged() const { return n_ok; }
+
+    // LQRTracker.cpp:53-65 (host, for spot checks), trajectory b
+    feedback_matrix_t interpolateGains(double t, size_t b = 0) const
+    {
+        const trajectory_data_t &td = tds[b];
+        t = std::clamp(t, 0., td.t);
+        const double dt = td.t / double(td.n_X() - 1);
+        const double a = std::fmod(t, dt) / dt;
+        const size_t i = std::min(size_t(t / dt), td.n_X() - 2);
+        const feedback_matrix_t &K0 = gain(b, i), &K1 = td.interpolatedInput() ? gain(b, i + 1) : K0;
+        feedback_matrix_t K;
+        for (size_t r = 0; r < NU; r++)
+            for (size_t c = 0; c < NX; c++)
+                K[r][c] = K0[r][c] + a * (K1[r][c] - K0[r][c]);
+        return K;
+    }
+    // LQRTracker.cpp:43-51 with trajectoryData.hpp:41-78 (host, for spot checks), trajectory b
+    void getInput(double t, const Model::state_vector_t &x, Model::input_vector_t &u, size_t b = 0) const
+    {
+        const trajectory_data_t &td = tds[b];
+        t = std::clamp(t, 0., td.t);
+        const double dt = td.t / double(td.n_X() - 1);
+        const double a = std::fmod(t, dt) / dt;
+        const size_t i = std::min(size_t(t / dt), td.n_X() - 2), j = td.interpolatedInput() ? i + 1 : i;
+        const feedback_matrix_t K = interpolateGains(t, b);
+        for (size_t r = 0; r < NU; r++)
+        {
+            double acc = 0.;
+            for (size_t c = 0; c < NX; c++)
+                acc += K[r][c] * (x[c] - (td.X[i][c] + a * (td.X[i + 1][c] - td.X[i][c])));
+            u[r] = -acc + (td.U[i][r] + a * (td.U[j][r] - td.U[i][r]));
+        }
+    }
+
+    // SC_tracking.cpp:48-75 for every trajectory at once, on the device: one flight per trajectory from x_start[b]
+    void track(const std::vector<Model::state_vector_t> &x_start, const Model::state_vector_t &x_final, lqr_track_result_t &out,
+               double time_step = 0.01, int n_record = 0, int write_steps = 30, int substeps = 20)
+    {
+        const int B = int(x_start.size());
+        double t_max = 0.;
+        for (const auto &td : tds)
+            t_max = std::max(t_max, td.t);
+        const int max_steps = int(std::ceil(t_max / time_step)) + 2;
+        check(scpp_hip_lqr_track(ctx, &x_start[0][0], x_final.data(), B, time_step, substeps, max_steps, n_record, write_steps, &out.n_finite),
+              "scpp_hip_lqr_track");
+        const size_t nB = size_t(B);
+        out.x.resize(nB);
+        out.u.resize(nB);
+        for (auto *v : {&out.t, &out.initial_error, &out.final_error, &out.max_deviation})
+            v->assign(nB, 0.);
+        out.steps.assign(nB, 0);
+        out.status.assign(nB, 0);
+        check(scpp_hip_lqr_track_download(ctx, &out.x[0][0], &out.u[0][0], out.t.data(), out.steps.data(), out.status.data(),
+                                          out.initial_error.data(), out.final_error.data(), out.max_deviation.data()),
+              "scpp_hip_lqr_track_download");
+        out.X_sim.clear();
+        out.U_sim.clear();
+        out.t_sim.clear();
+        if (n_record < 1)
+            return;
+        int nr = 0, cap = 0;
+        check(scpp_hip_lqr_track_record_size(ctx, &nr, &cap), "scpp_hip_lqr_track_record_size");
+        std::vector<double> X(size_t(nr) * cap * NX), U(size_t(nr) * cap * NU), t(size_t(nr) * cap);
+        std::vector<int32_t> n(size_t(nr), 0);
+        check(scpp_hip_lqr_track_record(ctx, X.data(), U.data(), t.data(), n.data()), "scpp_hip_lqr_track_record");
+        out.X_sim.resize(size_t(nr));
+        out.U_sim.resize(size_t(nr));
+        out.t_sim.resize(size_t(nr));
+        for (size_t b = 0; b < size_t(nr); b++)
+            for (size_t j = 0; j < size_t(n[b]); j++)
+            {
+                Model::state_vector_t xs;
+                Model::input_vector_t us;
+                std::copy(&X[(b * cap + j) * NX], &X[(b * cap + j) * NX] + NX, xs.begin());
+                std::copy(&U[(b * cap + j) * NU], &U[(b * cap + j) * NU] + NU, us.begin());
+                out.X_sim[b].push_back(xs);
+                out.U_sim[b].push_back(us);
+                out.t_sim[b].push_back(t[b * cap + j]);
+            }
+    }
+
+    std::array<double, NX> Q{};
+    std::array<double, NU> R{};
+    std::vector<feedback_matrix_t> gains; // [B][K]
+    std::vector<int32_t> status, iterations;
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != SCPP_OK)
+            throw std::runtime_error(std::string(what) + " failed with code " + std::to_string(rc));
+    }
+    Model::ptr_t model;
+    std::vector<trajectory_data_t> tds;
+    scpp_hip_lqr_ctx *ctx = nullptr;
+    int n_ok = 0;
+};
+
+} // namespace scpp

@@ -1,0 +1,134 @@
+// sc_tracking: the reference's SC_tracking executable (scpp/src/SC_tracking.cpp:17-124) on the device engine, batched.
+//   no arguments        : one trajectory from the shipped configuration, solved by SCAlgorithm, one LQR gain per node, the nonlinear plant
+//                         flown along it from x_init                                              (what the reference does)
+//   --batch N [--seed S]: N randomised initial states: N trajectories, N x K gains, N flights from those initial states
+//   --config DIR --out DIR --K n --device d --time-step s
+// Writes <out>/output/<Model>/SC_tracking/<time>/0/{X,U,t}.txt of instance 0 (every 30th step, like write_steps of the reference) and prints
+// gains/s, tracked plant steps/s and the distribution of the final error.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "lqr_tracker.hpp"
+#include "output.hpp"
+
+namespace fs = std::filesystem;
+
+static double seconds()
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+int main(int argc, char **argv)
+{
+    std::string config = "../scpp_amd/config", out = "..";
+    int batch = 0, K = 0, device = 0;
+    double time_step = 0.01;
+    unsigned long long seed = 20260927ull;
+    for (int i = 1; i < argc; i++)
+    {
+        auto next = [&]() -> const char * {
+            if (i + 1 >= argc)
+            {
+                std::fprintf(stderr, "missing value for %s\n", argv[i]);
+                std::exit(2);
+            }
+            return argv[++i];
+        };
+        if (!std::strcmp(argv[i], "--batch"))
+            batch = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--seed"))
+            seed = std::strtoull(next(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--config"))
+            config = next();
+        else if (!std::strcmp(argv[i], "--out"))
+            out = next();
+        else if (!std::strcmp(argv[i], "--K"))
+            K = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--device"))
+            device = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--time-step"))
+            time_step = std::atof(next());
+        else
+        {
+            std::fprintf(stderr, "unknown argument %s\n", argv[i]);
+            return 2;
+        }
+    }
+    try
+    {
+        Model::setParameterFolder(config);
+        auto model = std::make_shared<Model>();
+        model->loadParameters();
+
+        std::vector<Model::state_vector_t> x_inits;
+        if (batch <= 0)
+            x_inits.push_back(model->p.x_init);
+        for (int b = 0; b < batch; b++)
+        {
+            Model inst = *model;
+            inst.p.randomizeInitialState(seed, uint64_t(b));
+            x_inits.push_back(inst.p.x_init);
+        }
+        const size_t N = x_inits.size();
+
+        scpp::SCAlgorithm solver(model, int(N), device, K);
+        solver.initialize();
+        scpp::batch_result_t r;
+        double t0 = seconds();
+        solver.solveBatch(x_inits, r);
+        const double t_solve = seconds() - t0;
+        long conv = 0;
+        for (size_t b = 0; b < N; b++)
+            conv += r.converged[b];
+        std::printf("SC batch %zu: converged %ld in %.3f s\n", N, conv, t_solve);
+
+        // calculate LQR gains
+        t0 = seconds();
+        scpp::LQRTracker tracker(model, r.td, device);
+        const double t_gains = seconds() - t0;
+        const size_t nodes = N * r.td[0].n_X();
+        std::printf("Time, LQR gains: %.2f ms for %zu nodes (%d converged): %.0f gains/s (with context set-up and transfers)\n", 1e3 * t_gains, nodes,
+                    tracker.nodesConverged(), double(nodes) / t_gains);
+
+        // start simulation
+        scpp::lqr_track_result_t sim;
+        t0 = seconds();
+        tracker.track(x_inits, model->p.x_final, sim, time_step, 1, 30);
+        const double t_run = seconds() - t0;
+        long steps = 0;
+        std::vector<double> rel;
+        for (size_t b = 0; b < N; b++)
+        {
+            steps += sim.steps[b];
+            if (sim.status[b] != SCPP_LQR_NONFINITE && sim.initial_error[b] > 0.)
+                rel.push_back(100. * sim.final_error[b] / sim.initial_error[b]);
+        }
+        std::sort(rel.begin(), rel.end());
+        std::printf("Simulating %zu trajectories.\nFinished after %d steps (instance 0), %ld plant steps in %.2f ms: %.0f steps/s; %d of %zu flights finite\n", N,
+                    sim.steps[0] + 1, steps, 1e3 * t_run, double(steps) / t_run, sim.n_finite, N);
+        if (!rel.empty())
+            std::printf("Final error: %.4f%% (instance 0); over the batch min %.4f%% median %.4f%% max %.4f%%\n",
+                        100. * sim.final_error[0] / sim.initial_error[0], rel.front(), rel[rel.size() / 2], rel.back());
+
+        // write solution to files
+        const fs::path outputPath = fs::path(out) / "output" / Model::getModelName() / "SC_tracking" / scpp::getTimeString() / "0";
+        scpp::makeDir(outputPath);
+        scpp::writeRows(outputPath / "X.txt", sim.X_sim.at(0));
+        scpp::writeRows(outputPath / "U.txt", sim.U_sim.at(0));
+        {
+            std::ofstream f(outputPath / "t.txt");
+            for (double t : sim.t_sim.at(0))
+                f << t << "\n";
+        }
+        std::printf("output: %s\n", outputPath.string().c_str());
+    }
+    catch (const std::exception &e)
+    {
+        std::fprintf(stderr, "sc_tracking: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

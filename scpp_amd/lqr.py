@@ -1,0 +1,191 @@
+"""Batched mirrors of the reference's LQR front ends over the C ABI of include/scpp_hip_lqr.h:
+
+    LQRTracker     scpp_core/include/LQRTracker.hpp, src/LQRTracker.cpp:6-65 and the closed loop of scpp/src/SC_tracking.cpp:48-75
+    LQRAlgorithm   scpp_core/src/LQRAlgorithm.cpp:6-75 (one gain at the model's operating point)
+    LQRSim         scpp/src/LQR_sim.cpp:20-82 (without its input clipping, which does not compile for a two-input model)
+
+Every call handles B trajectories / closed loops.  The gains and the flights are computed by the HIP kernels of libscpp_lqr.so; only
+getInput (a spot check of one input) is host arithmetic.  There is no CPU fallback."""
+import math
+import os
+
+import numpy as np
+
+from ._lib import LqrContext
+from .parameter_server import ParameterServer
+
+
+def load_lqr_weights(model):
+    """LQRTracker::loadParameters (LQRTracker.cpp:30-41): state_weights / input_weights of <model>/LQR.info; Q = I, R = I without the file."""
+    path = os.path.join(model.getParameterFolder(), "LQR.info")
+    if not os.path.exists(path):
+        return np.ones(model.state_dim), np.ones(model.input_dim)
+    ps = ParameterServer(path)
+    return (np.array(ps.load_vector("state_weights", model.state_dim), dtype=np.float64),
+            np.array(ps.load_vector("input_weights", model.input_dim), dtype=np.float64))
+
+
+def si_flow_params(model):
+    """the flow-map parameters in SI units (the tracker flies the dimensional plant)"""
+    try:
+        return np.asarray(model.flow_params(nondimensionalize=False), dtype=np.float64)
+    except TypeError:  # Rocket2D has SI parameters only
+        return np.asarray(model.flow_params(), dtype=np.float64)
+
+
+class LQRTracker:
+    """Time-varying LQR along B trajectories: X [B][K][nx], U [B][K][nu] (first-order hold) or [B][K-1][nu] (zero-order hold), t [B], all in
+    SI units.  The gains are computed at construction, like the reference's constructor."""
+
+    def __init__(self, model, X, U, t, state_weights=None, input_weights=None, par=None, device=0, library=None, compute=True):
+        self.model = model
+        nx, nu = model.state_dim, model.input_dim
+        X = np.asarray(X, dtype=np.float64)
+        self.X = np.ascontiguousarray(X.reshape(-1, X.shape[-2], nx))
+        self.B, self.K = self.X.shape[0], self.X.shape[1]
+        self.U = np.ascontiguousarray(np.asarray(U, dtype=np.float64).reshape(self.B, -1, nu))
+        if self.U.shape[1] not in (self.K, self.K - 1):
+            raise ValueError(f"U has {self.U.shape[1]} rows per trajectory; K = {self.K} needs K (first-order hold) or K - 1 (zero-order hold)")
+        self.foh = self.U.shape[1] == self.K
+        self.t = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64).reshape(-1), (self.B,)))
+        q, r = load_lqr_weights(model)
+        self.Q = np.asarray(q if state_weights is None else state_weights, dtype=np.float64)
+        self.R = np.asarray(r if input_weights is None else input_weights, dtype=np.float64)
+        self.ctx = LqrContext(model.model_id, self.K, self.B, self.foh, device, library)
+        self.ctx.set_weights(self.Q, self.R)
+        self.ctx.set_flow_params(si_flow_params(model) if par is None else par)
+        self.ctx.set_trajectories(self.X, self.U, self.t)
+        self._gains = None
+        self.n_ok = None
+        if compute:
+            self.computeGains()
+
+    @classmethod
+    def from_algorithm(cls, alg, **kw):
+        """the tracker of every trajectory a solved SCAlgorithm / SCvxAlgorithm holds (SC_tracking.cpp:26-34)"""
+        sol = alg.getSolution()
+        U = sol["U"] if alg.opts.interpolate_input else sol["U"][:, :-1]
+        return cls(alg.model, sol["X"], U, sol["sigma"], **kw)
+
+    def computeGains(self):
+        self.n_ok = self.ctx.compute_gains()
+        self._gains = self.ctx.download_gains()
+        return self.n_ok
+
+    def setGains(self, G):
+        """user-supplied gains [B][K][nu][nx] instead of the computed ones"""
+        self.ctx.set_gains(G)
+        self._gains = dict(gains=np.array(G, dtype=np.float64).reshape(self.B, self.K, self.model.input_dim, self.model.state_dim), status=None, iters=None)
+
+    @property
+    def gains(self):
+        return self._gains["gains"]
+
+    @property
+    def status(self):
+        return self._gains["status"]
+
+    @property
+    def iterations(self):
+        return self._gains["iters"]
+
+    def getInput(self, t, x, b=0):
+        """LQRTracker::getInput (LQRTracker.cpp:43-65) of trajectory b, on the host: for spot checks of what the device loop applies"""
+        X, U, G, t_max = self.X[b], self.U[b], self.gains[b], float(self.t[b])
+        tc = min(max(float(t), 0.0), t_max)
+        dt = t_max / (self.K - 1)
+        a = math.fmod(tc, dt) / dt
+        i = min(int(tc / dt), self.K - 2)
+        j = i + 1 if self.foh else i
+        x_ref = X[i] + a * (X[i + 1] - X[i])
+        return -(G[i] + a * (G[j] - G[i])) @ (np.asarray(x, dtype=np.float64) - x_ref) + U[i] + a * (U[j] - U[i])
+
+    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30):
+        """The loop of SC_tracking.cpp:48-75 from x_start [B][nx], one flight per trajectory, on the device.  Returns x, u, t, steps, status,
+        err0, err1 (|x - x_final| at start / end), max_dev (largest |x - x_ref|), n_finite and, with n_record > 0, `record`."""
+        x_final = self.model.p.x_final if x_final is None else x_final
+        x_final = np.array(list(x_final), dtype=np.float64)
+        if max_steps is None:
+            max_steps = int(math.ceil(float(np.nanmax(self.t)) / time_step)) + 2
+        n_finite = self.ctx.track(x_start, x_final, time_step, substeps, max_steps, n_record, write_steps)
+        out = self.ctx.track_download()
+        out["n_finite"] = n_finite
+        if n_record > 0:
+            out["record"] = self.ctx.track_record()
+        return out
+
+    def close(self):
+        self.ctx.close()
+
+
+class LQRAlgorithm:
+    """LQRAlgorithm.cpp:6-75 for B states at once: one constant gain, linearised at the model's operating point."""
+
+    def __init__(self, model, batch_max=1, device=0, library=None):
+        if not hasattr(model, "getOperatingPoint"):
+            raise RuntimeError(f"{model.modelName} declares no operating point (the reference: Rocket2D only)")
+        self.model, self.batch_max, self.device, self.library = model, batch_max, device, library
+        self.initialized = False
+        self.x_init = self.x_final = self.u = None
+        self.loadParameters()
+
+    def loadParameters(self):
+        q, r = load_lqr_weights(self.model)
+        self.setStateWeights(q)
+        self.setInputWeights(r)
+
+    def setStateWeights(self, w):
+        self.Q = np.asarray(w, dtype=np.float64)
+
+    def setInputWeights(self, w):
+        self.R = np.asarray(w, dtype=np.float64)
+
+    def initialize(self):
+        """LQRAlgorithm.cpp:11-25: the gain kernel on a two-node constant 'trajectory' at the operating point"""
+        self.x_eq, self.u_eq = (np.asarray(v, dtype=np.float64) for v in self.model.getOperatingPoint())
+        X = np.tile(self.x_eq, (1, 2, 1))
+        U = np.tile(self.u_eq, (1, 2, 1))
+        trk = LQRTracker(self.model, X, U, [1.0], self.Q, self.R, device=self.device, library=self.library)
+        self.status, self.iterations = int(trk.status[0, 0]), int(trk.iterations[0, 0])
+        self.K = trk.gains[0, 0].copy()
+        trk.close()
+        if self.status != 0:
+            raise RuntimeError(f"LQR gain at the operating point failed with status {self.status}")
+        self.initialized = True
+        return self
+
+    def setInitialState(self, x):
+        self.x_init = np.asarray(x, dtype=np.float64).reshape(-1, self.model.state_dim)
+
+    def setFinalState(self, x):
+        self.x_final = np.asarray(x, dtype=np.float64).reshape(self.model.state_dim)
+
+    def solve(self):
+        """LQRAlgorithm.cpp:27-33"""
+        assert self.initialized
+        self.u = -(self.x_init - self.x_final) @ self.K.T + self.u_eq
+
+    def getSolution(self):
+        assert self.u is not None
+        return self.u
+
+
+class LQRSim:
+    """LQR_sim.cpp:20-82 for B closed loops on the device: u = -K (x - x_final) + u_eq until |x - x_final| < stop_tol or sim_time."""
+
+    def __init__(self, algorithm, sim_time=5.0, time_step=0.010, stop_tol=0.02):
+        self.alg, self.sim_time, self.time_step, self.stop_tol = algorithm, sim_time, time_step, stop_tol
+
+    def run(self, x_start, x_final=None, n_record=0, write_steps=30, substeps=20):
+        a = self.alg
+        assert a.initialized
+        x_start = np.asarray(x_start, dtype=np.float64).reshape(-1, a.model.state_dim)
+        B = x_start.shape[0]
+        x_final = np.asarray(a.model.p.x_final if x_final is None else x_final, dtype=np.float64)
+        trk = LQRTracker(a.model, np.tile(x_final, (B, 2, 1)), np.tile(a.u_eq, (B, 2, 1)), np.full(B, self.sim_time), a.Q, a.R,
+                         device=a.device, library=a.library, compute=False)
+        trk.setGains(np.tile(a.K, (B, 2, 1, 1)))
+        trk.ctx.set_stop_tolerance(self.stop_tol)
+        out = trk.track(x_start, x_final, self.time_step, substeps, None, n_record, write_steps)
+        trk.close()
+        return out

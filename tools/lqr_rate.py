@@ -1,0 +1,76 @@
+"""LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
+(N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
+
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+import scpp_amd  # noqa: E402
+
+
+def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None):
+    model = scpp_amd.RocketQuat().loadParameters()
+    x0 = model.randomized_initial_states(n)
+    alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
+    alg.solveStream(x0[:min(n, 256)])  # warm
+    t = time.perf_counter()
+    nconv = alg.solveStream(x0)
+    sol = alg.getStreamSolution()
+    t_solve = time.perf_counter() - t
+    alg.ctx.close()
+    trk = scpp_amd.LQRTracker(model, sol["X"], sol["U"], sol["sigma"], library=lqr_library, compute=False)
+    trk.ctx.compute_gains()  # warm (first launch loads the code object)
+    trk.ctx.synchronize()
+    tg = []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        n_ok = trk.ctx.compute_gains()  # returns after the status of every node is on the host
+        tg.append(time.perf_counter() - t)
+    trk.computeGains()
+    st, it = trk.status, trk.iterations
+    tt = []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        out = trk.track(x0)
+        tt.append(time.perf_counter() - t)
+    trk.close()
+    fin = out["status"] != -2
+    e = out["err1"][fin]
+    q = [float(v) for v in np.percentile(e, [5, 50, 95])] if e.size else []
+    return {
+        "workload": f"{n} RocketQuat trajectories x {K} nodes: LQR gains (tangent system, 26 x 26 Hamiltonian), {n} tracked flights, time step 0.01 s, 20 RKF78 steps each",
+        "n": int(n), "K": int(K), "scvx_converged": int(nconv), "solve_wall_s": t_solve,
+        "gain_nodes": int(st.size), "gain_status_ok": int(n_ok), "gain_status_iteration_limit": int((st == -1).sum()), "gain_status_nonfinite": int((st == -2).sum()),
+        "gains_nonfinite_values": int((~np.isfinite(trk.gains)).sum()),
+        "sign_iterations_per_node": float(it[st == 0].mean()) if (st == 0).any() else None, "sign_iterations_max": int(it.max()),
+        "gains_wall_s": min(tg), "gains_per_s": st.size / min(tg),
+        "track_wall_s": min(tt), "tracked_plant_steps": int(out["steps"].sum()), "tracked_plant_steps_per_s": float(out["steps"].sum() / min(tt)),
+        "flights_finite": int(out["n_finite"]), "flights_completed": int((out["status"] == 0).sum()), "flights_step_cap": int((out["status"] == 1).sum()),
+        "flights_nonfinite": int((out["status"] == -2).sum()),
+        "output_nonfinite_values": int(sum((~np.isfinite(out[k])).sum() for k in ("x", "u", "t", "err0", "err1", "max_dev"))),
+        "final_error_p5_p50_p95": q, "initial_error_p50": float(np.median(out["err0"][fin])) if fin.any() else None,
+        "max_excursion_p50": float(np.median(out["max_dev"][fin])) if fin.any() else None,
+        "timing": f"wall clock, best of {repeat}; gains include the download of the per-node status, flights the upload of the starts and the download of the results",
+    }
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=8192)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = measure(a.n, repeat=a.repeat)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
