@@ -12,6 +12,8 @@
  *       scpp::simulate (RKF78, fixed steps)   scpp_core/src/simulation.cpp:25-42
  *   LQRAlgorithm::initialize / solve, the loop of LQR_sim   LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82   the same, see scpp_hip_lqr_set_stop_tolerance
  *       (without LQR_sim's input clipping, which addresses u.z() of a two-input model and does not compile for Rocket2D)
+ *   nothing: the reference has no finite-horizon controller                                   scpp_hip_lqr_set_terminal_weights,
+ *       (the differential Riccati equation along the trajectory)               scpp_hip_lqr_compute_gains_riccati, _download_riccati
  *
  * Deviations, all deliberate:
  *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
@@ -22,6 +24,12 @@
  *     finite state and input (the reference throws); the errors are norms in double (the reference
  *     truncates them to size_t).
  *   - the record keeps every write_steps-th step.
+ *   - scpp_hip_lqr_compute_gains_riccati is an addition, not a replacement: -dP/dt = A'P + PA - P B R^-1 B'P + Q, P(T) = Qf, integrated
+ *     backwards segment by segment with fixed-step RKF78 (the tableau and solution weights of the plant step), on the full state of every model
+ *     (RocketQuat: 14 states, no tangent projection: the finite-horizon equation needs no stabilisability).  P is kept symmetric BY CONSTRUCTION
+ *     (P A and A'P are both formed, from the same products in the same order, and the quadratic term as S S' with S = P B R^-1/2); it is never
+ *     symmetrised.  Inside segment i the reference is x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]), j = i+1 (first-order hold) or i
+ *     (zero-order hold), a in [0, 1]; the segment index is that of the segment being integrated and is never recomputed from the time.
  *
  * Conventions as in scpp_hip.h: every function returns 0 or a negative SCPP_E_* code, nothing throws; host buffers are caller-owned, float64
  * (int32 where said), C-contiguous; one host thread per context.  All work goes on the context's own stream; nothing synchronises the device.
@@ -70,7 +78,19 @@ extern "C"
     int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *ctx, const void *dX, const void *dU, const void *dt, int B, int u_rows);
     /* one gain per (instance, node); *n_ok (optional) = nodes with status 0.  SCPP_E_STATE without trajectories or flow parameters. */
     int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *ctx, int *n_ok);
-    /* gains [B][K][nu][nx], status [B][K] int32, iters [B][K] int32 (sign iterations); any pointer may be NULL */
+    /* diagonal of the terminal weight Qf of the finite-horizon gains; NULL: Qf = Q (the default).  Every entry finite and > 0, else SCPP_E_ARG. */
+    int scpp_hip_lqr_set_terminal_weights(scpp_hip_lqr_ctx *ctx, const double *qf /* [nx] */);
+    /* finite-horizon gains: one Riccati sweep per trajectory from P(T) = Qf, steps >= 1 RKF78 steps per segment (SCPP_E_ARG otherwise), one
+       K_k = R^-1 B_k'P(t_k) per node with B_k at (X[k], U[min(k, nU-1)]), node K-1: R^-1 B'Qf; full [nu][nx] shape.  Gains, status and the
+       count land where scpp_hip_lqr_download_gains reads them (the count: RKF78 steps behind the node, (K-1-k) steps) and scpp_hip_lqr_track
+       flies them.  A trajectory with a non-finite node, input or flight time gets SCPP_LQR_NONFINITE and zero gains on every node; a P that
+       turns non-finite in segment k does the same for node k and every earlier node.  keep_p != 0 also keeps P(t_k) for
+       scpp_hip_lqr_download_riccati (the buffer, B K nx nx doubles, is allocated on the first such request).  *n_ok (optional) = nodes with
+       status 0.  SCPP_E_STATE as scpp_hip_lqr_compute_gains. */
+    int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *ctx, int steps, int keep_p, int *n_ok);
+    /* P [B][K][nx][nx] of the last sweep (zeros on failed nodes); SCPP_E_STATE unless the last gain computation was a sweep with keep_p != 0 */
+    int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *ctx, double *P);
+    /* gains [B][K][nu][nx], status [B][K] int32, iters [B][K] int32 (sign iterations, or RKF78 steps behind the node); any pointer may be NULL */
     int scpp_hip_lqr_download_gains(scpp_hip_lqr_ctx *ctx, double *gains, int *status, int *iters);
     /* user-supplied gains [B][K][nu][nx] for the trajectories set before; non-finite entries are refused (SCPP_E_ARG) */
     int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *ctx, const double *gains);

@@ -481,6 +481,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_set_flow_params", "scpp_hip_lqr_set_trajectories", "scpp_hip_lqr_set_trajectories_device", "scpp_hip_lqr_compute_gains",
     "scpp_hip_lqr_download_gains", "scpp_hip_lqr_set_gains", "scpp_hip_lqr_set_stop_tolerance", "scpp_hip_lqr_track", "scpp_hip_lqr_track_download",
     "scpp_hip_lqr_track_record_size", "scpp_hip_lqr_track_record", "scpp_hip_lqr_synchronize",
+    "scpp_hip_lqr_set_terminal_weights", "scpp_hip_lqr_compute_gains_riccati", "scpp_hip_lqr_download_riccati",
 ]
 _lqr_libs = {}
 
@@ -561,6 +562,23 @@ class LqrContext:
         n = C.c_int()
         _chk(self.lib.scpp_hip_lqr_compute_gains(self.h, C.byref(n)), "lqr_compute_gains")
         return int(n.value)
+
+    def set_terminal_weights(self, qf=None):
+        """diagonal of Qf for the finite-horizon gains; None: Qf = Q"""
+        if qf is not None:
+            qf = np.ascontiguousarray(qf, dtype=np.float64).reshape(self.nx)
+        _chk(self.lib.scpp_hip_lqr_set_terminal_weights(self.h, _p(qf)), "lqr_set_terminal_weights")
+
+    def compute_gains_riccati(self, steps=5, keep_p=False):
+        """finite-horizon gains (one Riccati sweep per trajectory); returns the number of nodes with status 0"""
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_compute_gains_riccati(self.h, int(steps), int(bool(keep_p)), C.byref(n)), "lqr_compute_gains_riccati")
+        return int(n.value)
+
+    def download_riccati(self):
+        P = np.zeros((self.B, self.K, self.nx, self.nx))
+        _chk(self.lib.scpp_hip_lqr_download_riccati(self.h, _p(P)), "lqr_download_riccati")
+        return P
 
     def download_gains(self, with_status=True):
         G = np.zeros((self.B, self.K, self.nu, self.nx))

@@ -2,6 +2,7 @@
 // Built as a library of its own (libscpp_lqr.so; with -DSCPP_HIP_EMU: the CPU emulation of the same source), see DESIGN.md 4.8.
 #include "../../../include/scpp_hip_lqr.h"
 #include "lqr_kernels.h"
+#include "lqr_riccati_kernel.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -41,6 +42,9 @@ struct scpp_hip_lqr_ctx
     double *X = nullptr, *U = nullptr, *T = nullptr;          // owned copies (scpp_hip_lqr_set_trajectories)
     const double *tX = nullptr, *tU = nullptr, *tT = nullptr; // the trajectories in use: the owned copies or the caller's device memory
     double *par = nullptr, *q = nullptr, *r = nullptr, *G = nullptr;
+    double *qf = nullptr, *P = nullptr; // terminal weights (used when have_qf) and P(t_k) of the last Riccati sweep, allocated on request only
+    size_t P_cap = 0;                   // doubles allocated behind P
+    bool have_qf = false, have_p = false;
     int *gstatus = nullptr, *giters = nullptr;
     double *xs = nullptr, *xf = nullptr, *ox = nullptr, *ou = nullptr, *os = nullptr;
     int *oi = nullptr;
@@ -149,6 +153,7 @@ int scpp_hip_lqr_create(scpp_hip_lqr_ctx **out, int device_id, int model_id, int
     rc |= devAlloc(&c->par, B * c->np);
     rc |= devAlloc(&c->q, nx);
     rc |= devAlloc(&c->r, nu);
+    rc |= devAlloc(&c->qf, nx);
     rc |= devAlloc(&c->G, B * K * nu * nx);
     rc |= devAlloc(&c->gstatus, B * K);
     rc |= devAlloc(&c->giters, B * K);
@@ -183,7 +188,7 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     DeviceGuard guard(c->device);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn};
+    void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -223,7 +228,7 @@ int scpp_hip_lqr_set_weights(scpp_hip_lqr_ctx *c, const double *q, const double 
     CHECK_HIP(hipMemcpyAsync(c->r, r, size_t(c->nu) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
     if (c->gains_computed)
-        c->have_gains = c->gains_computed = false;
+        c->have_gains = c->gains_computed = c->have_p = false;
     return SCPP_OK;
 }
 
@@ -238,7 +243,7 @@ int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
     c->par_rows = B;
     c->have_par = true;
     if (c->gains_computed)
-        c->have_gains = c->gains_computed = false;
+        c->have_gains = c->gains_computed = c->have_p = false;
     return SCPP_OK;
 }
 
@@ -257,7 +262,7 @@ int scpp_hip_lqr_set_trajectories(scpp_hip_lqr_ctx *c, const double *X, const do
     c->uRows = c->nU;
     c->B = B;
     c->have_traj = true;
-    c->have_gains = c->gains_computed = false;
+    c->have_gains = c->gains_computed = c->have_p = false;
     return SCPP_OK;
 }
 
@@ -271,7 +276,7 @@ int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *c, const void *dX, co
     c->uRows = u_rows;
     c->B = B;
     c->have_traj = true;
-    c->have_gains = c->gains_computed = false;
+    c->have_gains = c->gains_computed = c->have_p = false;
     return SCPP_OK;
 }
 
@@ -297,6 +302,7 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
     if (hipGetLastError() != hipSuccess)
         return SCPP_E_HIP;
     c->have_gains = c->gains_computed = true;
+    c->have_p = false;
     if (n_ok)
     {
         HostBuf<int> st(static_cast<size_t>(nodes));
@@ -309,6 +315,90 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
             n += (st.p[i] == SCPP_LQR_OK);
         *n_ok = n;
     }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_terminal_weights(scpp_hip_lqr_ctx *c, const double *qf)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (qf)
+    {
+        for (int i = 0; i < c->nx; i++)
+            if (!std::isfinite(qf[i]) || !(qf[i] > 0.))
+                return SCPP_E_ARG;
+        DeviceGuard guard(c->device);
+        CHECK_HIP(hipMemcpyAsync(c->qf, qf, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+    }
+    c->have_qf = qf != nullptr;
+    if (c->gains_computed)
+        c->have_gains = c->gains_computed = c->have_p = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *c, int steps, int keep_p, int *n_ok)
+{
+    if (!c || steps < 1)
+        return SCPP_E_ARG;
+    if (!c->have_traj || !c->have_par)
+        return SCPP_E_STATE;
+    if (c->par_rows != 1 && c->par_rows != c->B)
+        return SCPP_E_STATE;
+    if (long(c->K - 1) * steps > 0x7fffffffL)
+        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
+    DeviceGuard guard(c->device);
+    const long nodes = long(c->B) * c->K;
+    const size_t p_need = size_t(nodes) * c->nx * c->nx;
+    c->have_p = false;
+    if (keep_p && p_need > c->P_cap)
+    {
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        if (c->P)
+            (void)hipFree(c->P);
+        c->P = nullptr;
+        c->P_cap = 0;
+        if (devAlloc(&c->P, p_need))
+            return SCPP_E_HIP;
+        c->P_cap = p_need;
+    }
+    int rc = withLqrPlugin(c->model, [&](auto pl) {
+        using P = decltype(pl);
+        hipLaunchKernelGGL((lqr_riccati_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
+                           (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
+                           (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep_p ? c->P : (double *)nullptr);
+        return 0;
+    });
+    if (rc)
+        return rc;
+    if (hipGetLastError() != hipSuccess)
+        return SCPP_E_HIP;
+    c->have_gains = c->gains_computed = true;
+    c->have_p = keep_p != 0;
+    if (n_ok)
+    {
+        HostBuf<int> st(static_cast<size_t>(nodes));
+        if (!st.p)
+            return SCPP_E_HIP;
+        CHECK_HIP(hipMemcpyAsync(st.p, c->gstatus, size_t(nodes) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        int n = 0;
+        for (long i = 0; i < nodes; i++)
+            n += (st.p[i] == SCPP_LQR_OK);
+        *n_ok = n;
+    }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *c, double *P)
+{
+    if (!c || !P)
+        return SCPP_E_ARG;
+    if (!c->have_p)
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    CHECK_HIP(hipMemcpyAsync(P, c->P, size_t(c->B) * c->K * c->nx * c->nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
     return SCPP_OK;
 }
 
@@ -345,7 +435,7 @@ int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *c, const double *gains)
     CHECK_HIP(hipMemcpyAsync(c->G, gains, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream));
     c->have_gains = true;
-    c->gains_computed = false;
+    c->gains_computed = c->have_p = false;
     return SCPP_OK;
 }
 

@@ -27,6 +27,18 @@ struct lqr_track_result_t
     std::vector<std::vector<double>> t_sim;
 };
 
+// which gain law the tracker computes.  finite_horizon = false (the default, the reference's): one frozen-time gain per node.  true: the
+// differential Riccati equation swept backwards along each trajectory from P(T) = Qf (scpp_hip_lqr_compute_gains_riccati), riccati_steps
+// RKF78 steps per segment; terminal_weights: the diagonal of Qf, empty: LQR.info's terminal_weights if present, else Qf = Q;
+// keep_riccati: P(t_k) is downloaded into LQRTracker::riccati.
+struct lqr_gain_options_t
+{
+    bool finite_horizon = false;
+    int riccati_steps = 5;
+    bool keep_riccati = false;
+    std::vector<double> terminal_weights;
+};
+
 class LQRTracker
 {
 public:
@@ -36,8 +48,8 @@ public:
     // LQRTracker.cpp:6-28 for every trajectory of `tds` (all with the same K and hold): the gains are computed here
     // `weights`: (state_weights [NX], input_weights [NU]) instead of those of LQR.info
     LQRTracker(Model::ptr_t model_, const std::vector<trajectory_data_t> &tds_, int device = 0,
-               const std::pair<std::array<double, NX>, std::array<double, NU>> *weights = nullptr)
-        : model(std::move(model_)), tds(tds_)
+               const std::pair<std::array<double, NX>, std::array<double, NU>> *weights = nullptr, const lqr_gain_options_t &options = {})
+        : opts(options), model(std::move(model_)), tds(tds_)
     {
         if (tds.empty() || tds[0].n_X() < 2)
             throw std::invalid_argument("LQRTracker: at least one trajectory of at least two nodes");
@@ -69,15 +81,29 @@ public:
             t[size_t(b)] = td.t;
         }
         check(scpp_hip_lqr_set_trajectories(ctx, X.data(), U.data(), t.data(), B), "scpp_hip_lqr_set_trajectories");
-        check(scpp_hip_lqr_compute_gains(ctx, &n_ok), "scpp_hip_lqr_compute_gains");
+        if (opts.finite_horizon)
+        {
+            std::vector<double> qf = opts.terminal_weights.empty() ? loadTerminalWeights() : opts.terminal_weights;
+            if (!qf.empty() && qf.size() != NX)
+                throw std::invalid_argument("LQRTracker: terminal_weights needs one entry per state");
+            check(scpp_hip_lqr_set_terminal_weights(ctx, qf.empty() ? nullptr : qf.data()), "scpp_hip_lqr_set_terminal_weights");
+            check(scpp_hip_lqr_compute_gains_riccati(ctx, opts.riccati_steps, opts.keep_riccati ? 1 : 0, &n_ok), "scpp_hip_lqr_compute_gains_riccati");
+            if (opts.keep_riccati)
+            {
+                riccati.resize(size_t(B) * K * NX * NX);
+                check(scpp_hip_lqr_download_riccati(ctx, riccati.data()), "scpp_hip_lqr_download_riccati");
+            }
+        }
+        else
+            check(scpp_hip_lqr_compute_gains(ctx, &n_ok), "scpp_hip_lqr_compute_gains");
         gains.resize(size_t(B) * K);
         status.resize(size_t(B) * K);
         iterations.resize(size_t(B) * K);
         check(scpp_hip_lqr_download_gains(ctx, &gains[0][0][0], status.data(), iterations.data()), "scpp_hip_lqr_download_gains");
     }
     LQRTracker(Model::ptr_t model_, const trajectory_data_t &td, int device = 0,
-               const std::pair<std::array<double, NX>, std::array<double, NU>> *weights = nullptr)
-        : LQRTracker(std::move(model_), std::vector<trajectory_data_t>{td}, device, weights)
+               const std::pair<std::array<double, NX>, std::array<double, NU>> *weights = nullptr, const lqr_gain_options_t &options = {})
+        : LQRTracker(std::move(model_), std::vector<trajectory_data_t>{td}, device, weights, options)
     {
     }
     ~LQRTracker()
@@ -99,6 +125,20 @@ public:
         ParameterServer param(file);
         param.loadMatrix("state_weights", Q.data(), int(NX));
         param.loadMatrix("input_weights", R.data(), int(NU));
+    }
+
+    // the optional terminal_weights vector of LQR.info; empty without the file or the entry (Qf = Q)
+    static std::vector<double> loadTerminalWeights()
+    {
+        const std::string file = Model::getParameterFolder() + "/LQR.info";
+        if (!std::filesystem::exists(file))
+            return {};
+        ParameterServer param(file);
+        if (!param.has("terminal_weights"))
+            return {};
+        std::vector<double> qf(NX);
+        param.loadMatrix("terminal_weights", qf.data(), int(NX));
+        return qf;
     }
 
     const feedback_matrix_t &gain(size_t b, size_t k) const { return gains[b * tds[0].n_X() + k]; }
@@ -187,7 +227,9 @@ public:
     std::array<double, NX> Q{};
     std::array<double, NU> R{};
     std::vector<feedback_matrix_t> gains; // [B][K]
-    std::vector<int32_t> status, iterations;
+    std::vector<int32_t> status, iterations; // iterations: sign iterations, or RKF78 steps behind the node (finite horizon)
+    std::vector<double> riccati;             // [B][K][NX][NX], finite horizon with keep_riccati only
+    lqr_gain_options_t opts;
 
 private:
     static void check(int rc, const char *what)

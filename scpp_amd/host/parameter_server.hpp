@@ -96,6 +96,9 @@ public:
         }
     }
 
+    // whether the file has the key at all (optional entries)
+    bool has(const std::string &name) const { return root.children.find(name) != root.children.end(); }
+
     template <typename T>
     void loadScalar(const std::string &name, T &scalar) const
     {

@@ -3,6 +3,8 @@
 //                         flown along it from x_init                                              (what the reference does)
 //   --batch N [--seed S]: N randomised initial states: N trajectories, N x K gains, N flights from those initial states
 //   --config DIR --out DIR --K n --device d --time-step s
+//   --gains frozen|riccati : frozen (default): one frozen-time infinite-horizon gain per node (the reference's); riccati: finite-horizon gains,
+//                         the differential Riccati equation swept backwards along each trajectory; --riccati-steps n RKF78 steps per segment (5)
 // Writes <out>/output/<Model>/SC_tracking/<time>/0/{X,U,t}.txt of instance 0 (every 30th step, like write_steps of the reference) and prints
 // gains/s, tracked plant steps/s and the distribution of the final error.
 #include <algorithm>
@@ -25,6 +27,7 @@ int main(int argc, char **argv)
 {
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
+    scpp::lqr_gain_options_t gain_opts;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
     for (int i = 1; i < argc; i++)
@@ -51,6 +54,18 @@ int main(int argc, char **argv)
             device = std::atoi(next());
         else if (!std::strcmp(argv[i], "--time-step"))
             time_step = std::atof(next());
+        else if (!std::strcmp(argv[i], "--gains"))
+        {
+            const std::string which = next();
+            if (which != "frozen" && which != "riccati")
+            {
+                std::fprintf(stderr, "--gains %s: frozen or riccati\n", which.c_str());
+                return 2;
+            }
+            gain_opts.finite_horizon = which == "riccati";
+        }
+        else if (!std::strcmp(argv[i], "--riccati-steps"))
+            gain_opts.riccati_steps = std::atoi(next());
         else
         {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -87,9 +102,14 @@ int main(int argc, char **argv)
 
         // calculate LQR gains
         t0 = seconds();
-        scpp::LQRTracker tracker(model, r.td, device);
+        scpp::LQRTracker tracker(model, r.td, device, nullptr, gain_opts);
         const double t_gains = seconds() - t0;
         const size_t nodes = N * r.td[0].n_X();
+        if (gain_opts.finite_horizon)
+            std::printf("Gains: riccati (finite horizon, %d RKF78 steps per segment, %zu Riccati right-hand sides)\n", gain_opts.riccati_steps,
+                        N * (r.td[0].n_X() - 1) * size_t(gain_opts.riccati_steps) * 13);
+        else
+            std::printf("Gains: frozen (one infinite-horizon gain per node)\n");
         std::printf("Time, LQR gains: %.2f ms for %zu nodes (%d converged): %.0f gains/s (with context set-up and transfers)\n", 1e3 * t_gains, nodes,
                     tracker.nodesConverged(), double(nodes) / t_gains);
 

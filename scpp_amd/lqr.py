@@ -25,6 +25,18 @@ def load_lqr_weights(model):
             np.array(ps.load_vector("input_weights", model.input_dim), dtype=np.float64))
 
 
+def load_lqr_terminal_weights(model):
+    """the optional terminal_weights vector of <model>/LQR.info (diagonal of Qf of the finite-horizon gains); None when the file or the
+    vector is absent: Qf = Q"""
+    path = os.path.join(model.getParameterFolder(), "LQR.info")
+    if not os.path.exists(path):
+        return None
+    ps = ParameterServer(path)
+    if "terminal_weights" not in ps.tree:
+        return None
+    return np.array(ps.load_vector("terminal_weights", model.state_dim), dtype=np.float64)
+
+
 def si_flow_params(model):
     """the flow-map parameters in SI units (the tracker flies the dimensional plant)"""
     try:
@@ -35,9 +47,18 @@ def si_flow_params(model):
 
 class LQRTracker:
     """Time-varying LQR along B trajectories: X [B][K][nx], U [B][K][nu] (first-order hold) or [B][K-1][nu] (zero-order hold), t [B], all in
-    SI units.  The gains are computed at construction, like the reference's constructor."""
+    SI units.  The gains are computed at construction, like the reference's constructor.
 
-    def __init__(self, model, X, U, t, state_weights=None, input_weights=None, par=None, device=0, library=None, compute=True):
+    horizon="infinite" (the default, the reference's): one frozen-time gain per node, each from an algebraic Riccati equation of its own.
+    horizon="finite": the differential Riccati equation swept backwards along each trajectory from P(T) = Qf (terminal_weights, the
+    diagonal; None: LQR.info's terminal_weights if present, else Qf = Q), riccati_steps RKF78 steps per segment; keep_riccati=True also
+    keeps P(t_k) (the `riccati` property, [B][K][nx][nx])."""
+
+    def __init__(self, model, X, U, t, state_weights=None, input_weights=None, par=None, device=0, library=None, compute=True,
+                 horizon="infinite", terminal_weights=None, riccati_steps=5, keep_riccati=False):
+        if horizon not in ("infinite", "finite"):
+            raise ValueError(f"horizon = {horizon!r}: 'infinite' or 'finite'")
+        self.horizon, self.riccati_steps, self.keep_riccati = horizon, int(riccati_steps), bool(keep_riccati)
         self.model = model
         nx, nu = model.state_dim, model.input_dim
         X = np.asarray(X, dtype=np.float64)
@@ -53,6 +74,12 @@ class LQRTracker:
         self.R = np.asarray(r if input_weights is None else input_weights, dtype=np.float64)
         self.ctx = LqrContext(model.model_id, self.K, self.B, self.foh, device, library)
         self.ctx.set_weights(self.Q, self.R)
+        self.Qf = None
+        if horizon == "finite":
+            qf = load_lqr_terminal_weights(model) if terminal_weights is None else terminal_weights
+            self.Qf = self.Q.copy() if qf is None else np.asarray(qf, dtype=np.float64)
+            self.ctx.set_terminal_weights(self.Qf)
+        self._riccati = None
         self.ctx.set_flow_params(si_flow_params(model) if par is None else par)
         self.ctx.set_trajectories(self.X, self.U, self.t)
         self._gains = None
@@ -68,13 +95,33 @@ class LQRTracker:
         return cls(alg.model, sol["X"], U, sol["sigma"], **kw)
 
     def computeGains(self):
+        if self.horizon == "finite":
+            return self.computeGainsRiccati()
         self.n_ok = self.ctx.compute_gains()
         self._gains = self.ctx.download_gains()
+        self._riccati = None
         return self.n_ok
+
+    def computeGainsRiccati(self, steps=None, keep=None):
+        """finite-horizon gains of every trajectory (one Riccati sweep each, on the device); they replace the gains held so far"""
+        steps = self.riccati_steps if steps is None else int(steps)
+        keep = self.keep_riccati if keep is None else bool(keep)
+        self.n_ok = self.ctx.compute_gains_riccati(steps, keep)
+        self._gains = self.ctx.download_gains()
+        self._riccati = self.ctx.download_riccati() if keep else None
+        return self.n_ok
+
+    @property
+    def riccati(self):
+        """P(t_k) [B][K][nx][nx] of the last sweep; needs keep_riccati=True (or computeGainsRiccati(keep=True))"""
+        if self._riccati is None:
+            raise RuntimeError("no Riccati solution kept: construct with horizon='finite', keep_riccati=True")
+        return self._riccati
 
     def setGains(self, G):
         """user-supplied gains [B][K][nu][nx] instead of the computed ones"""
         self.ctx.set_gains(G)
+        self._riccati = None
         self._gains = dict(gains=np.array(G, dtype=np.float64).reshape(self.B, self.K, self.model.input_dim, self.model.state_dim), status=None, iters=None)
 
     @property

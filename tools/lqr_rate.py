@@ -1,7 +1,10 @@
 """LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
-    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--out FILE]
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--out FILE]
+
+--riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
+segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
 """
 import argparse
 import json
@@ -16,7 +19,7 @@ import numpy as np  # noqa: E402
 import scpp_amd  # noqa: E402
 
 
-def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None):
+def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -41,11 +44,12 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None):
         t = time.perf_counter()
         out = trk.track(x0)
         tt.append(time.perf_counter() - t)
+    ric = riccati_leg(trk, x0, int(riccati), repeat) if riccati else {}
     trk.close()
     fin = out["status"] != -2
     e = out["err1"][fin]
     q = [float(v) for v in np.percentile(e, [5, 50, 95])] if e.size else []
-    return {
+    res = {
         "workload": f"{n} RocketQuat trajectories x {K} nodes: LQR gains (tangent system, 26 x 26 Hamiltonian), {n} tracked flights, time step 0.01 s, 20 RKF78 steps each",
         "n": int(n), "K": int(K), "scvx_converged": int(nconv), "solve_wall_s": t_solve,
         "gain_nodes": int(st.size), "gain_status_ok": int(n_ok), "gain_status_iteration_limit": int((st == -1).sum()), "gain_status_nonfinite": int((st == -2).sum()),
@@ -60,15 +64,45 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None):
         "max_excursion_p50": float(np.median(out["max_dev"][fin])) if fin.any() else None,
         "timing": f"wall clock, best of {repeat}; gains include the download of the per-node status, flights the upload of the starts and the download of the results",
     }
+    res.update(ric)
+    return res
+
+
+def riccati_leg(trk, x0, steps, repeat):
+    """finite-horizon gains on the tracker's trajectories, then the same flights under them"""
+    trk.ctx.compute_gains_riccati(steps)  # warm
+    tr = []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        n_ok = trk.ctx.compute_gains_riccati(steps)  # returns after the status of every node is on the host
+        tr.append(time.perf_counter() - t)
+    trk.computeGainsRiccati(steps, keep=False)
+    st, it = trk.status, trk.iterations
+    out = trk.track(x0)
+    fin = out["status"] != -2
+    e = out["err1"][fin]
+    rhs = trk.B * (trk.K - 1) * steps * 13
+    return {
+        "riccati_steps_per_segment": steps, "riccati_wall_s": min(tr), "riccati_rhs": int(rhs), "riccati_rhs_per_s": rhs / min(tr),
+        "riccati_nodes": int(st.size), "riccati_status_ok": int(n_ok), "riccati_status_nonfinite": int((st == -2).sum()),
+        "riccati_status_other": int(((st != 0) & (st != -2)).sum()), "riccati_gains_nonfinite_values": int((~np.isfinite(trk.gains)).sum()),
+        "riccati_steps_behind_node0": int(it[:, 0].max()),
+        "riccati_flights_finite": int(out["n_finite"]), "riccati_flights_completed": int((out["status"] == 0).sum()),
+        "riccati_flights_step_cap": int((out["status"] == 1).sum()), "riccati_flights_nonfinite": int((out["status"] == -2).sum()),
+        "riccati_output_nonfinite_values": int(sum((~np.isfinite(out[k])).sum() for k in ("x", "u", "t", "err0", "err1", "max_dev"))),
+        "riccati_final_error_p5_p50_p95": [float(v) for v in np.percentile(e, [5, 50, 95])] if e.size else [],
+        "riccati_max_excursion_p50": float(np.median(out["max_dev"][fin])) if fin.any() else None,
+    }
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--riccati", type=int, default=0, help="RKF78 steps per segment of the finite-horizon leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = measure(a.n, repeat=a.repeat)
+    res = measure(a.n, repeat=a.repeat, riccati=a.riccati)
     line = json.dumps(res)
     print(line)
     if a.out:
