@@ -14,6 +14,8 @@
  *       (without LQR_sim's input clipping, which addresses u.z() of a two-input model and does not compile for Rocket2D)
  *   nothing: the reference has no finite-horizon controller                                   scpp_hip_lqr_set_terminal_weights,
  *       (the differential Riccati equation along the trajectory)               scpp_hip_lqr_compute_gains_riccati, _download_riccati
+ *   nothing: the reference has no covariance analysis                                         scpp_hip_lqr_set_covariance_inputs,
+ *       (the closed-loop Lyapunov equation along the trajectory)               scpp_hip_lqr_propagate_covariance, _download_covariance
  *
  * Deviations, all deliberate:
  *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
@@ -30,6 +32,17 @@
  *     (P A and A'P are both formed, from the same products in the same order, and the quadratic term as S S' with S = P B R^-1/2); it is never
  *     symmetrised.  Inside segment i the reference is x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]), j = i+1 (first-order hold) or i
  *     (zero-order hold), a in [0, 1]; the segment index is that of the segment being integrated and is never recomputed from the time.
+ *   - scpp_hip_lqr_propagate_covariance is an addition as well: linear covariance analysis of the closed loop,
+ *     dS/dt = A_cl(t) S + S A_cl(t)' + W, S(0) = S0, A_cl(t) = A(t) - B(t) K(t), W = diag(w) a constant disturbance intensity, w >= 0 (default 0),
+ *     S0 a full symmetric matrix.  For one trajectory of K nodes and flight time T, dt = T / (K - 1); the sweep runs segment by segment from
+ *     segment 0 up to K-2.  Inside segment i at fraction a in [0, 1]: x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]),
+ *     K_t = G[i] + a (G[j] - G[i]), j = i+1 (first-order hold) or i (zero-order hold): exactly the interpolation the tracking kernel applies to
+ *     state, input and gain.  The segment index is the loop's and is never recomputed from the time.  A, B are the generated Jacobian rows at
+ *     (x, u), on the full state of every model (RocketQuat: 14 states).  G is whatever gains the context holds: frozen-time, Riccati or
+ *     scpp_hip_lqr_set_gains.  The integrator is fixed-step RKF78 with the plant step's tableau and 8th-order weights, steps >= 1 steps per
+ *     segment; stage s of step n sits at a = (n + c_s) / steps.  Node k records S(t_k) and the input covariance G[k] S(t_k) G[k]' with the
+ *     node's own gain; node 0 records S0 exactly.  S is kept symmetric BY CONSTRUCTION (A_cl S and S A_cl' are both formed, from the same
+ *     products in the same order); it is never symmetrised, which is why S0 has to be symmetric to the bit.
  *
  * Conventions as in scpp_hip.h: every function returns 0 or a negative SCPP_E_* code, nothing throws; host buffers are caller-owned, float64
  * (int32 where said), C-contiguous; one host thread per context.  All work goes on the context's own stream; nothing synchronises the device.
@@ -53,6 +66,7 @@ extern "C"
 /* per-node gain status and per-instance tracking status */
 #define SCPP_LQR_OK 0
 #define SCPP_LQR_STEP_CAP 1         /* tracking: stopped by max_steps before the flight time */
+#define SCPP_LQR_GAINS_INCOMPLETE 2 /* covariance, informational: some node of the trajectory has a gain status != 0, i.e. a zero gain; the sweep ran on it */
 #define SCPP_LQR_ITERATION_LIMIT -1 /* gains: 101 sign iterations without convergence (LQR.cpp:19-20) */
 #define SCPP_LQR_NONFINITE -2       /* gains: singular or non-finite Hamiltonian; tracking: non-finite state */
 
@@ -94,6 +108,25 @@ extern "C"
     int scpp_hip_lqr_download_gains(scpp_hip_lqr_ctx *ctx, double *gains, int *status, int *iters);
     /* user-supplied gains [B][K][nu][nx] for the trajectories set before; non-finite entries are refused (SCPP_E_ARG) */
     int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *ctx, const double *gains);
+    /* inputs of the covariance sweep: sigma0 [B][nx][nx], the initial state covariance of every trajectory (B == 1: one matrix for all of
+       them), and w [nx], the diagonal of the disturbance intensity W (NULL: W = 0).  SCPP_E_ARG for a non-finite sigma0 entry, a sigma0 that
+       is not symmetric TO THE BIT (the kernel relies on it), a negative diagonal entry of sigma0, a negative or non-finite w, B neither 1
+       nor the number of trajectories; SCPP_E_STATE without trajectories.  The inputs stay until they are set again. */
+    int scpp_hip_lqr_set_covariance_inputs(scpp_hip_lqr_ctx *ctx, const double *sigma0 /* [B or 1][nx][nx] */, int B, const double *w /* [nx] or NULL */);
+    /* one forward sweep per trajectory under the gains the context holds, steps >= 1 RKF78 steps per segment (SCPP_E_ARG otherwise).
+       SCPP_E_STATE without trajectories, flow parameters, gains or covariance inputs (or with rows for another number of trajectories).
+       Per-trajectory status: SCPP_LQR_OK; SCPP_LQR_GAINS_INCOMPLETE; SCPP_LQR_NONFINITE: a non-finite node, input, flight time or gain (zeros
+       in every output), or an S (or input covariance) that turned non-finite in segment k (node k+1 and every later node, and final_cov, are
+       zeros; earlier nodes keep their values).  Nothing non-finite is ever written.  keep_cov != 0 also keeps S(t_k) of every node (the
+       buffer, B K nx nx doubles, is allocated on the first such request).  *n_ok (optional) = trajectories with status 0.  The sweep changes
+       neither the gains nor the tracking state; computing or setting gains, new trajectories, flow parameters or covariance inputs
+       invalidate it. */
+    int scpp_hip_lqr_propagate_covariance(scpp_hip_lqr_ctx *ctx, int steps, int keep_cov, int *n_ok);
+    /* state_std [B][K][nx] = sqrt of the diagonal of S(t_k) (an entry negative from rounding counts as 0), input_cov [B][K][nu][nu] =
+       G[k] S(t_k) G[k]' (symmetric to rounding), final_cov [B][nx][nx] = S(T), status [B] int32, cov [B][K][nx][nx] = S(t_k); any pointer may
+       be NULL.  SCPP_E_STATE before a sweep, and for cov after a sweep with keep_cov == 0. */
+    int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *ctx, double *state_std /* [B][K][nx] */, double *input_cov /* [B][K][nu][nu] */,
+                                         double *final_cov /* [B][nx][nx] */, int *status /* [B] */, double *cov /* [B][K][nx][nx], keep_cov only */);
     /* regulator mode (LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82): with stop_tol > 0 a loop also ends once |x - x_final| < stop_tol.  The
        caller sets a constant two-node "trajectory" (X = x_final, U = u_eq, t = sim_time) and the one gain of the operating point
        (scpp_hip_lqr_set_gains), so that u = -K (x - x_final) + u_eq; the same two kernels, no third.  0 (the default) switches it off. */

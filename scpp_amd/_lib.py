@@ -476,12 +476,14 @@ class Context:
 
 # ---- the LQR tracker: a library of its own (include/scpp_hip_lqr.h, csrc/lqr/), bound separately ----
 LQR_OK, LQR_STEP_CAP, LQR_ITERATION_LIMIT, LQR_NONFINITE = 0, 1, -1, -2
+LQR_GAINS_INCOMPLETE = 2
 LQR_SYMBOLS = [
     "scpp_hip_lqr_version", "scpp_hip_lqr_create", "scpp_hip_lqr_destroy", "scpp_hip_lqr_dims", "scpp_hip_lqr_set_weights",
     "scpp_hip_lqr_set_flow_params", "scpp_hip_lqr_set_trajectories", "scpp_hip_lqr_set_trajectories_device", "scpp_hip_lqr_compute_gains",
     "scpp_hip_lqr_download_gains", "scpp_hip_lqr_set_gains", "scpp_hip_lqr_set_stop_tolerance", "scpp_hip_lqr_track", "scpp_hip_lqr_track_download",
     "scpp_hip_lqr_track_record_size", "scpp_hip_lqr_track_record", "scpp_hip_lqr_synchronize",
     "scpp_hip_lqr_set_terminal_weights", "scpp_hip_lqr_compute_gains_riccati", "scpp_hip_lqr_download_riccati",
+    "scpp_hip_lqr_set_covariance_inputs", "scpp_hip_lqr_propagate_covariance", "scpp_hip_lqr_download_covariance",
 ]
 _lqr_libs = {}
 
@@ -579,6 +581,29 @@ class LqrContext:
         P = np.zeros((self.B, self.K, self.nx, self.nx))
         _chk(self.lib.scpp_hip_lqr_download_riccati(self.h, _p(P)), "lqr_download_riccati")
         return P
+
+    def set_covariance_inputs(self, sigma0, w=None):
+        """sigma0 [B][nx][nx] or one [nx][nx] for every trajectory (symmetric to the bit), w [nx] >= 0 the diagonal of the disturbance
+        intensity (None: 0)"""
+        sigma0 = np.ascontiguousarray(sigma0, dtype=np.float64).reshape(-1, self.nx, self.nx)
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(self.nx)
+        _chk(self.lib.scpp_hip_lqr_set_covariance_inputs(self.h, _p(sigma0), int(sigma0.shape[0]), _p(w)), "lqr_set_covariance_inputs")
+
+    def propagate_covariance(self, steps=5, keep_cov=False):
+        """one closed-loop covariance sweep per trajectory under the gains held; returns the number of trajectories with status 0"""
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_propagate_covariance(self.h, int(steps), int(bool(keep_cov)), C.byref(n)), "lqr_propagate_covariance")
+        return int(n.value)
+
+    def download_covariance(self, with_cov=False):
+        out = dict(state_std=np.zeros((self.B, self.K, self.nx)), input_cov=np.zeros((self.B, self.K, self.nu, self.nu)),
+                   final_cov=np.zeros((self.B, self.nx, self.nx)), status=np.zeros(self.B, dtype=np.int32))
+        if with_cov:
+            out["cov"] = np.zeros((self.B, self.K, self.nx, self.nx))
+        _chk(self.lib.scpp_hip_lqr_download_covariance(self.h, *[_p(out[k]) for k in ("state_std", "input_cov", "final_cov", "status")],
+                                                       _p(out.get("cov"))), "lqr_download_covariance")
+        return out
 
     def download_gains(self, with_status=True):
         G = np.zeros((self.B, self.K, self.nu, self.nx))

@@ -3,6 +3,7 @@
 #include "../../../include/scpp_hip_lqr.h"
 #include "lqr_kernels.h"
 #include "lqr_riccati_kernel.h"
+#include "lqr_covariance_kernel.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -46,6 +47,13 @@ struct scpp_hip_lqr_ctx
     size_t P_cap = 0;                   // doubles allocated behind P
     bool have_qf = false, have_p = false;
     int *gstatus = nullptr, *giters = nullptr;
+    // covariance sweep (scpp_hip_lqr_propagate_covariance): inputs and outputs are allocated by the first scpp_hip_lqr_set_covariance_inputs,
+    // the full S(t_k) by the first keep_cov request
+    double *s0 = nullptr, *cw = nullptr, *cstd = nullptr, *cin = nullptr, *cfin = nullptr, *cov = nullptr;
+    int *cstatus = nullptr;
+    size_t cov_cap = 0;
+    int s0_rows = 0; // rows given to scpp_hip_lqr_set_covariance_inputs: 1 (shared) or the number of trajectories
+    bool have_cov_in = false, have_cov = false, cov_kept = false;
     double *xs = nullptr, *xf = nullptr, *ox = nullptr, *ou = nullptr, *os = nullptr;
     int *oi = nullptr;
     double *rx = nullptr, *ru = nullptr, *rt = nullptr;
@@ -188,7 +196,8 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     DeviceGuard guard(c->device);
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
-    void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn};
+    void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -228,7 +237,7 @@ int scpp_hip_lqr_set_weights(scpp_hip_lqr_ctx *c, const double *q, const double 
     CHECK_HIP(hipMemcpyAsync(c->r, r, size_t(c->nu) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
     if (c->gains_computed)
-        c->have_gains = c->gains_computed = c->have_p = false;
+        c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
     return SCPP_OK;
 }
 
@@ -242,8 +251,9 @@ int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
     c->par_stride = (B == 1) ? 0 : c->np;
     c->par_rows = B;
     c->have_par = true;
+    c->have_cov = false;
     if (c->gains_computed)
-        c->have_gains = c->gains_computed = c->have_p = false;
+        c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
     return SCPP_OK;
 }
 
@@ -262,7 +272,7 @@ int scpp_hip_lqr_set_trajectories(scpp_hip_lqr_ctx *c, const double *X, const do
     c->uRows = c->nU;
     c->B = B;
     c->have_traj = true;
-    c->have_gains = c->gains_computed = c->have_p = false;
+    c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
     return SCPP_OK;
 }
 
@@ -276,7 +286,7 @@ int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *c, const void *dX, co
     c->uRows = u_rows;
     c->B = B;
     c->have_traj = true;
-    c->have_gains = c->gains_computed = c->have_p = false;
+    c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
     return SCPP_OK;
 }
 
@@ -302,7 +312,7 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
     if (hipGetLastError() != hipSuccess)
         return SCPP_E_HIP;
     c->have_gains = c->gains_computed = true;
-    c->have_p = false;
+    c->have_p = c->have_cov = false;
     if (n_ok)
     {
         HostBuf<int> st(static_cast<size_t>(nodes));
@@ -333,7 +343,7 @@ int scpp_hip_lqr_set_terminal_weights(scpp_hip_lqr_ctx *c, const double *qf)
     }
     c->have_qf = qf != nullptr;
     if (c->gains_computed)
-        c->have_gains = c->gains_computed = c->have_p = false;
+        c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
     return SCPP_OK;
 }
 
@@ -375,6 +385,7 @@ int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *c, int steps, int keep_
         return SCPP_E_HIP;
     c->have_gains = c->gains_computed = true;
     c->have_p = keep_p != 0;
+    c->have_cov = false;
     if (n_ok)
     {
         HostBuf<int> st(static_cast<size_t>(nodes));
@@ -435,7 +446,129 @@ int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *c, const double *gains)
     CHECK_HIP(hipMemcpyAsync(c->G, gains, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream));
     c->have_gains = true;
-    c->gains_computed = c->have_p = false;
+    c->gains_computed = c->have_p = c->have_cov = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_covariance_inputs(scpp_hip_lqr_ctx *c, const double *sigma0, int B, const double *w)
+{
+    if (!c || !sigma0)
+        return SCPP_E_ARG;
+    if (!c->have_traj)
+        return SCPP_E_STATE; // B is judged against the number of trajectories
+    if (B != 1 && B != c->B)
+        return SCPP_E_ARG;
+    const size_t nx = size_t(c->nx), nn = nx * nx;
+    for (size_t b = 0; b < size_t(B); b++)
+    {
+        const double *s = sigma0 + b * nn;
+        if (!allFinite(s, nn))
+            return SCPP_E_ARG;
+        for (size_t i = 0; i < nx; i++)
+        {
+            if (s[i * nx + i] < 0.)
+                return SCPP_E_ARG;
+            for (size_t j = 0; j < i; j++)
+                if (s[i * nx + j] != s[j * nx + i])
+                    return SCPP_E_ARG; // symmetric to the bit: the kernel reads one half for the other
+        }
+    }
+    for (size_t i = 0; w && i < nx; i++)
+        if (!std::isfinite(w[i]) || w[i] < 0.)
+            return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    if (!c->s0)
+    {
+        const size_t Bm = size_t(c->Bmax), nu = size_t(c->nu);
+        int rc = devAlloc(&c->s0, Bm * nn) | devAlloc(&c->cw, nx) | devAlloc(&c->cstd, Bm * c->K * nx) | devAlloc(&c->cin, Bm * c->K * nu * nu) |
+                 devAlloc(&c->cfin, Bm * nn) | devAlloc(&c->cstatus, Bm);
+        if (rc)
+            return SCPP_E_HIP;
+    }
+    HostBuf<double> zero(nx);
+    if (!zero.p)
+        return SCPP_E_HIP;
+    for (size_t i = 0; i < nx; i++)
+        zero.p[i] = 0.;
+    CHECK_HIP(hipMemcpyAsync(c->s0, sigma0, size_t(B) * nn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipMemcpyAsync(c->cw, w ? w : zero.p, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
+    c->s0_rows = B;
+    c->have_cov_in = true;
+    c->have_cov = false;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_propagate_covariance(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok)
+{
+    if (!c || steps < 1)
+        return SCPP_E_ARG;
+    if (!c->have_traj || !c->have_par || !c->have_gains || !c->have_cov_in)
+        return SCPP_E_STATE;
+    if ((c->par_rows != 1 && c->par_rows != c->B) || (c->s0_rows != 1 && c->s0_rows != c->B))
+        return SCPP_E_STATE; // rows for another number of trajectories
+    DeviceGuard guard(c->device);
+    const size_t need = size_t(c->B) * c->K * c->nx * c->nx;
+    c->have_cov = false;
+    if (keep_cov && need > c->cov_cap)
+    {
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        if (c->cov)
+            (void)hipFree(c->cov);
+        c->cov = nullptr;
+        c->cov_cap = 0;
+        if (devAlloc(&c->cov, need))
+            return SCPP_E_HIP;
+        c->cov_cap = need;
+    }
+    int rc = withLqrPlugin(c->model, [&](auto pl) {
+        using P = decltype(pl);
+        hipLaunchKernelGGL((lqr_covariance_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
+                           (const double *)c->par, c->par_stride, (const double *)c->G, (const int *)(c->gains_computed ? c->gstatus : nullptr),
+                           (const double *)c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, (const double *)c->cw, c->cstd, c->cin, c->cfin, c->cstatus,
+                           keep_cov ? c->cov : (double *)nullptr);
+        return 0;
+    });
+    if (rc)
+        return rc;
+    if (hipGetLastError() != hipSuccess)
+        return SCPP_E_HIP;
+    c->have_cov = true;
+    c->cov_kept = keep_cov != 0;
+    if (n_ok)
+    {
+        HostBuf<int> st(static_cast<size_t>(c->B));
+        if (!st.p)
+            return SCPP_E_HIP;
+        CHECK_HIP(hipMemcpyAsync(st.p, c->cstatus, size_t(c->B) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream));
+        int n = 0;
+        for (int b = 0; b < c->B; b++)
+            n += (st.p[b] == SCPP_LQR_OK);
+        *n_ok = n;
+    }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *c, double *state_std, double *input_cov, double *final_cov, int *status, double *cov)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_cov || (cov && !c->cov_kept))
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t B = size_t(c->B), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
+    if (state_std)
+        CHECK_HIP(hipMemcpyAsync(state_std, c->cstd, B * K * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (input_cov)
+        CHECK_HIP(hipMemcpyAsync(input_cov, c->cin, B * K * nu * nu * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (final_cov)
+        CHECK_HIP(hipMemcpyAsync(final_cov, c->cfin, B * nx * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (status)
+        CHECK_HIP(hipMemcpyAsync(status, c->cstatus, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (cov)
+        CHECK_HIP(hipMemcpyAsync(cov, c->cov, B * K * nx * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
     return SCPP_OK;
 }
 

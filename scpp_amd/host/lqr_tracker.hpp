@@ -39,6 +39,27 @@ struct lqr_gain_options_t
     std::vector<double> terminal_weights;
 };
 
+// the closed-loop covariance sweep (scpp_hip_lqr_propagate_covariance): dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0, under the gains the tracker
+// holds.  sigma0: one symmetric [NX][NX] matrix for every trajectory or [B][NX][NX], row-major; disturbance: the diagonal of W, empty: W = 0;
+// steps: RKF78 steps per segment; keep: S(t_k) of every node is downloaded into lqr_covariance_result_t::cov.
+struct lqr_covariance_options_t
+{
+    std::vector<double> sigma0;
+    std::vector<double> disturbance;
+    int steps = 5;
+    bool keep = false;
+};
+
+struct lqr_covariance_result_t
+{
+    std::vector<double> state_std; // [B][K][NX]  sqrt of the diagonal of S(t_k)
+    std::vector<double> input_cov; // [B][K][NU][NU]  G[k] S(t_k) G[k]'
+    std::vector<double> final_cov; // [B][NX][NX]
+    std::vector<double> cov;       // [B][K][NX][NX], keep only
+    std::vector<int32_t> status;   // [B]: SCPP_LQR_OK, SCPP_LQR_GAINS_INCOMPLETE, SCPP_LQR_NONFINITE
+    int n_ok = 0;
+};
+
 class LQRTracker
 {
 public:
@@ -222,6 +243,42 @@ public:
                 out.U_sim[b].push_back(us);
                 out.t_sim[b].push_back(t[b * cap + j]);
             }
+    }
+
+    // linear covariance analysis of every trajectory at once, on the device, under the gains held; changes neither gains nor flights
+    void covariance(const lqr_covariance_options_t &o, lqr_covariance_result_t &out)
+    {
+        const size_t B = tds.size(), K = tds[0].n_X();
+        if (o.sigma0.size() != NX * NX && o.sigma0.size() != B * NX * NX)
+            throw std::invalid_argument("LQRTracker::covariance: sigma0 is one NX x NX matrix, or one per trajectory");
+        if (!o.disturbance.empty() && o.disturbance.size() != NX)
+            throw std::invalid_argument("LQRTracker::covariance: disturbance needs one entry per state");
+        check(scpp_hip_lqr_set_covariance_inputs(ctx, o.sigma0.data(), int(o.sigma0.size() / (NX * NX)),
+                                                 o.disturbance.empty() ? nullptr : o.disturbance.data()),
+              "scpp_hip_lqr_set_covariance_inputs");
+        check(scpp_hip_lqr_propagate_covariance(ctx, o.steps, o.keep ? 1 : 0, &out.n_ok), "scpp_hip_lqr_propagate_covariance");
+        out.state_std.assign(B * K * NX, 0.);
+        out.input_cov.assign(B * K * NU * NU, 0.);
+        out.final_cov.assign(B * NX * NX, 0.);
+        out.status.assign(B, 0);
+        out.cov.assign(o.keep ? B * K * NX * NX : 0, 0.);
+        check(scpp_hip_lqr_download_covariance(ctx, out.state_std.data(), out.input_cov.data(), out.final_cov.data(), out.status.data(),
+                                               o.keep ? out.cov.data() : nullptr),
+              "scpp_hip_lqr_download_covariance");
+    }
+
+    // the optional vector `name` of LQR.info (initial_std, disturbance_std: one entry per state); empty without the file or the entry
+    static std::vector<double> loadOptionalVector(const std::string &name)
+    {
+        const std::string file = Model::getParameterFolder() + "/LQR.info";
+        if (!std::filesystem::exists(file))
+            return {};
+        ParameterServer param(file);
+        if (!param.has(name))
+            return {};
+        std::vector<double> v(NX);
+        param.loadMatrix(name, v.data(), int(NX));
+        return v;
     }
 
     std::array<double, NX> Q{};

@@ -5,6 +5,10 @@
 //   --config DIR --out DIR --K n --device d --time-step s
 //   --gains frozen|riccati : frozen (default): one frozen-time infinite-horizon gain per node (the reference's); riccati: finite-horizon gains,
 //                         the differential Riccati equation swept backwards along each trajectory; --riccati-steps n RKF78 steps per segment (5)
+//   --covariance        : also the closed-loop covariance sweep along every trajectory under those gains (scpp_hip_lqr_propagate_covariance):
+//                         S(0) = diag(initial_std)^2 and W = diag(disturbance_std)^2 from the optional vectors initial_std / disturbance_std of
+//                         LQR.info (absent: 0); --covariance-steps n RKF78 steps per segment (5).  Writes state_std.txt (one node per row) and
+//                         input_cov.txt (one node per row, the nu x nu matrix row-major) of instance 0 next to X.txt
 // Writes <out>/output/<Model>/SC_tracking/<time>/0/{X,U,t}.txt of instance 0 (every 30th step, like write_steps of the reference) and prints
 // gains/s, tracked plant steps/s and the distribution of the final error.
 #include <algorithm>
@@ -28,6 +32,8 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
+    bool covariance = false;
+    int covariance_steps = 5;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
     for (int i = 1; i < argc; i++)
@@ -66,6 +72,10 @@ int main(int argc, char **argv)
         }
         else if (!std::strcmp(argv[i], "--riccati-steps"))
             gain_opts.riccati_steps = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--covariance"))
+            covariance = true;
+        else if (!std::strcmp(argv[i], "--covariance-steps"))
+            covariance_steps = std::atoi(next());
         else
         {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -113,6 +123,28 @@ int main(int argc, char **argv)
         std::printf("Time, LQR gains: %.2f ms for %zu nodes (%d converged): %.0f gains/s (with context set-up and transfers)\n", 1e3 * t_gains, nodes,
                     tracker.nodesConverged(), double(nodes) / t_gains);
 
+        // closed-loop covariance along every trajectory
+        scpp::lqr_covariance_result_t cov;
+        if (covariance)
+        {
+            constexpr size_t NX = Model::state_dim;
+            scpp::lqr_covariance_options_t co;
+            co.steps = covariance_steps;
+            const std::vector<double> sd0 = scpp::LQRTracker::loadOptionalVector("initial_std");
+            co.disturbance = scpp::LQRTracker::loadOptionalVector("disturbance_std");
+            co.sigma0.assign(NX * NX, 0.);
+            for (size_t j = 0; j < sd0.size(); j++)
+                co.sigma0[j * NX + j] = sd0[j] * sd0[j];
+            for (double &v : co.disturbance)
+                v *= v;
+            t0 = seconds();
+            tracker.covariance(co, cov);
+            const double t_cov = seconds() - t0;
+            const size_t rhs = N * (r.td[0].n_X() - 1) * size_t(covariance_steps) * 13;
+            std::printf("Covariance: %d RKF78 steps per segment, %zu right-hand sides in %.2f ms (%d of %zu trajectories with status 0)\n", covariance_steps,
+                        rhs, 1e3 * t_cov, cov.n_ok, N);
+        }
+
         // start simulation
         scpp::lqr_track_result_t sim;
         t0 = seconds();
@@ -142,6 +174,19 @@ int main(int argc, char **argv)
             std::ofstream f(outputPath / "t.txt");
             for (double t : sim.t_sim.at(0))
                 f << t << "\n";
+        }
+        if (covariance)
+        {
+            constexpr size_t NX = Model::state_dim, NU = Model::input_dim;
+            const size_t Kn = r.td[0].n_X();
+            std::vector<std::vector<double>> sd(Kn), ic(Kn);
+            for (size_t k = 0; k < Kn; k++)
+            {
+                sd[k].assign(&cov.state_std[k * NX], &cov.state_std[k * NX] + NX);
+                ic[k].assign(&cov.input_cov[k * NU * NU], &cov.input_cov[k * NU * NU] + NU * NU);
+            }
+            scpp::writeRows(outputPath / "state_std.txt", sd);
+            scpp::writeRows(outputPath / "input_cov.txt", ic);
         }
         std::printf("output: %s\n", outputPath.string().c_str());
     }

@@ -37,6 +37,16 @@ def load_lqr_terminal_weights(model):
     return np.array(ps.load_vector("terminal_weights", model.state_dim), dtype=np.float64)
 
 
+def load_lqr_covariance_inputs(model):
+    """the optional initial_std and disturbance_std vectors of <model>/LQR.info (standard deviations of the initial state and square roots
+    of the disturbance intensity, one entry per state); None for whichever the file does not have"""
+    path = os.path.join(model.getParameterFolder(), "LQR.info")
+    if not os.path.exists(path):
+        return None, None
+    ps = ParameterServer(path)
+    return tuple(np.array(ps.load_vector(k, model.state_dim), dtype=np.float64) if ps.has(k) else None for k in ("initial_std", "disturbance_std"))
+
+
 def si_flow_params(model):
     """the flow-map parameters in SI units (the tracker flies the dimensional plant)"""
     try:
@@ -159,6 +169,17 @@ class LQRTracker:
         out["n_finite"] = n_finite
         if n_record > 0:
             out["record"] = self.ctx.track_record()
+        return out
+
+    def covariance(self, sigma0, disturbance=None, steps=5, keep=False):
+        """Linear covariance analysis of the closed loop under the gains held, one forward sweep per trajectory on the device:
+        dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0 ([nx][nx] for every trajectory or [B][nx][nx], symmetric), A_cl = A - B K_t,
+        W = diag(disturbance) (None: 0), `steps` RKF78 steps per segment.  Returns state_std [B][K][nx], input_cov [B][K][nu][nu]
+        (G[k] S(t_k) G[k]'), final_cov [B][nx][nx], status [B], n_ok and, with keep=True, cov [B][K][nx][nx]."""
+        self.ctx.set_covariance_inputs(sigma0, disturbance)
+        n_ok = self.ctx.propagate_covariance(steps, keep)
+        out = self.ctx.download_covariance(keep)
+        out["n_ok"] = n_ok
         return out
 
     def close(self):

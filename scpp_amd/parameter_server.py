@@ -35,6 +35,10 @@ class ParameterServer:
                 stack.append(node["children"])
                 i += 1
 
+    def has(self, name):
+        """whether the file has the key at all (optional entries)"""
+        return name in self.tree
+
     def _get(self, name):
         if name not in self.tree or self.tree[name]["value"] is None:
             raise RuntimeError(f"WARNING: Failed to load scalar type: {name}!")

@@ -1,10 +1,15 @@
 """LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
-    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--out FILE]
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
 segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
+
+--covariance STEPS (measure(covariance=STEPS)) adds the closed-loop covariance sweep of every trajectory (STEPS RKF78 steps per segment) under
+the gains the tracker holds at that point: the Riccati gains when --riccati is given too, else the frozen-time ones.  It only ADDS keys
+(covariance_*).  The initial covariance is diagonal: 1 % of the largest |state| over the batch (a floor of 1e-3) as the standard deviation of
+every state; the disturbance intensity is 1 % of that variance per second.
 """
 import argparse
 import json
@@ -19,7 +24,7 @@ import numpy as np  # noqa: E402
 import scpp_amd  # noqa: E402
 
 
-def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None):
+def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -45,6 +50,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
         out = trk.track(x0)
         tt.append(time.perf_counter() - t)
     ric = riccati_leg(trk, x0, int(riccati), repeat) if riccati else {}
+    if covariance:
+        ric.update(covariance_leg(trk, int(covariance), repeat, "riccati" if riccati else "frozen"))
     trk.close()
     fin = out["status"] != -2
     e = out["err1"][fin]
@@ -95,14 +102,46 @@ def riccati_leg(trk, x0, steps, repeat):
     }
 
 
+def covariance_leg(trk, steps, repeat, law):
+    """the closed-loop covariance sweep on the tracker's trajectories under the gains it holds"""
+    sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
+    sigma0, w = np.diag(sd * sd), 0.01 * sd * sd
+    trk.ctx.set_covariance_inputs(sigma0, w)
+    trk.ctx.propagate_covariance(steps)  # warm
+    tc = []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        n_ok = trk.ctx.propagate_covariance(steps)  # returns after the status of every trajectory is on the host
+        tc.append(time.perf_counter() - t)
+    o = trk.ctx.download_covariance()
+    st = o["status"]
+    ok = st != -2
+    rhs = trk.B * (trk.K - 1) * steps * 13
+    pos = np.sqrt((o["state_std"][ok, -1, 1:4] ** 2).sum(axis=1))  # RocketQuat: states 1..3 are the position
+    # inputs 0..2 are the thrust vector (input 3: the roll torque); 3 sigma of its norm at every node
+    thrust = 3.0 * np.sqrt(np.maximum(np.trace(o["input_cov"][ok][:, :, :3, :3], axis1=2, axis2=3), 0.0)) if ok.any() else np.zeros(0)
+    return {
+        "covariance_steps_per_segment": steps, "covariance_gains": law, "covariance_wall_s": min(tc), "covariance_rhs": int(rhs),
+        "covariance_rhs_per_s": rhs / min(tc), "covariance_trajectories": int(st.size), "covariance_nodes": int(st.size * trk.K),
+        "covariance_status_ok": int(n_ok), "covariance_status_gains_incomplete": int((st == 2).sum()),
+        "covariance_status_nonfinite": int((st == -2).sum()), "covariance_status_other": int(((st != 0) & (st != 2) & (st != -2)).sum()),
+        "covariance_nonfinite_values": int(sum((~np.isfinite(o[k])).sum() for k in ("state_std", "input_cov", "final_cov"))),
+        "covariance_final_position_std_p5_p50_p95": [float(v) for v in np.percentile(pos, [5, 50, 95])] if pos.size else [],
+        "covariance_thrust_3sigma_max": float(thrust.max()) if thrust.size else 0.0,
+        "covariance_thrust_3sigma_p50": float(np.median(thrust.max(axis=1))) if thrust.size else 0.0,
+        "covariance_initial_std": [float(v) for v in sd],
+    }
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--riccati", type=int, default=0, help="RKF78 steps per segment of the finite-horizon leg (0: no such leg)")
+    ap.add_argument("--covariance", type=int, default=0, help="RKF78 steps per segment of the covariance leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = measure(a.n, repeat=a.repeat, riccati=a.riccati)
+    res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance)
     line = json.dumps(res)
     print(line)
     if a.out:
