@@ -3,9 +3,7 @@
 //
 //   dS/dt = A_cl(t) S + S A_cl(t)' + W,   S(0) = S0,   A_cl(t) = A(t) - B(t) K(t),   input covariance of node k: G[k] S(t_k) G[k]'
 //
-// Mapping: that of lqr_riccati_kernel.h.  ONE WAVEFRONT PER TRAJECTORY; S, padded with zeros, is one 16 x 16 FP64 tile in the accumulator layout of
-// v_mfma_f64_16x16x4_f64 (lane l, register r: row (l >> 4) + 4 r, column l & 15), and so is each of the 13 RKF78 stage slopes.  S being symmetric,
-// register c of lane l is the lane's share of chunk c of the B operand (S[4c + g][col]) and of the A operand (S[col][4c + g]) alike.  Lane r < nx
+// Mapping: ONE WAVEFRONT PER TRAJECTORY, S one 16 x 16 FP64 tile in the accumulator layout (lqr_tile_sweep.h).  Lane r < nx
 // evaluates row r of [A | B] at the stage's reference, forms row r of A_cl = A - B K_t (nu nx FMAs, K_t interpolated from an LDS copy of the
 // segment's two node gains) and writes it to a zero-padded LDS tile, which is kept TRANSPOSED (the row goes down a column: consecutive lanes,
 // consecutive addresses), so that the read-back in the accumulator pattern, At[(4c + g)][col] = A_cl[col][4c + g], is the lane's share of the A
@@ -15,7 +13,7 @@
 //     F  = (M1 + M2) + W
 // S STAYS SYMMETRIC BY CONSTRUCTION (bitwise); nothing is symmetrised.
 #pragma once
-#include "lqr_riccati_kernel.h"
+#include "lqr_tile_sweep.h"
 
 namespace scpp
 {
@@ -28,7 +26,7 @@ struct CovarianceLds
 {
     double At[RT * RT];         // At[c][r] = A_cl[r][c]; rows and columns >= nx stay zero
     double G0[4 * RT], G1[4 * RT]; // gains of the segment's two nodes, [a][c]
-    double x0[RT], x1[RT], u0[4], u1[4];
+    SegmentLds seg;
 };
 
 // F = (A_cl S + S A_cl') + W in the accumulator layout; Ac = the lane's share of the transposed A_cl tile, wd = its share of W
@@ -46,6 +44,34 @@ __device__ __forceinline__ d4_t covarianceRhs(const d4_t Sn, const double (&Ac)[
     for (int r = 0; r < 4; r++)
         F[r] = (M1[r] + M2[r]) + wd[r];
     return F;
+}
+
+// lane r < NX: row r of A_cl = A - B K_t at the reference's point a of the segment -> LDS, transposed; afterwards every lane holds its share of the tile
+template <class P>
+__device__ __forceinline__ void closedLoopJacobian(CovarianceLds &lds, int lane, double a, const double *p, const double *aux, double (&Ac)[4])
+{
+    constexpr int NX = P::Model::NX, NU = P::Model::NU;
+    const int g = lane >> 4, col = lane & 15;
+    if (lane < NX)
+    {
+        double x[NX], u[NU], jr[NX + NU];
+        interpolateSegment(lds.seg, a, x, u);
+        jacobianRow<P>(lane, x, u, p, aux, jr);
+#pragma unroll
+        for (int c = 0; c < NX; c++)
+        {
+            double acl = jr[c];
+#pragma unroll
+            for (int q = 0; q < NU; q++)
+                acl -= jr[NX + q] * (lds.G0[q * RT + c] + a * (lds.G1[q * RT + c] - lds.G0[q * RT + c]));
+            lds.At[c * RT + lane] = acl;
+        }
+    }
+    WAVE_SYNC();
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        Ac[c] = lds.At[(4 * c + g) * RT + col];
+    WAVE_SYNC();
 }
 
 // One sweep per trajectory.  X [B][K][nx], U [B][uRows][nu] (nU rows used), T [B], par [B][np], G [B][K][nu][nx], gstatus [B][K] (nullptr: gains
@@ -79,21 +105,17 @@ __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int
     for (int j = 0; j < NP; j++)
         p[j] = par[b * par_stride + j];
     JR::prepare(p, aux);
-    d4_t wd, Sc;
+    const d4_t wd = diagonalTile<NX>(lane, w);
+    d4_t Sc;
 #pragma unroll
     for (int r = 0; r < 4; r++)
     {
         const int row = 4 * r + g;
         const bool in = row < NX && col < NX;
-        wd[r] = (in && row == col) ? w[in ? col : 0] : 0.;
         Sc[r] = in ? S0[b * s0_stride + (in ? row * NX + col : 0)] : 0.;
     }
     const double t_max = T[b];
-    int bad = isFinite(t_max) ? 0 : 1, incomplete = 0;
-    for (int e = lane; e < K * NX; e += WAVE)
-        bad |= isFinite(Xb[e]) ? 0 : 1;
-    for (int e = lane; e < nU * NU; e += WAVE)
-        bad |= isFinite(Ub[e]) ? 0 : 1;
+    int bad = referenceNonFinite<NX, NU>(lane, t_max, Xb, Ub, K, nU), incomplete = 0;
     for (int e = lane; e < K * NU * NX; e += WAVE)
         bad |= isFinite(Gb[e]) ? 0 : 1;
     if (gstatus)
@@ -111,16 +133,7 @@ __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int
         {
             // ---- segment i = k-1: S(t_i) -> S(t_k), `steps` RKF78 steps ----
             const int i = k - 1, ju = foh ? k : i;
-            if (lane < NX)
-            {
-                lds.x0[lane] = Xb[i * NX + lane];
-                lds.x1[lane] = Xb[k * NX + lane];
-            }
-            if (lane < NU)
-            {
-                lds.u0[lane] = Ub[i * NU + lane];
-                lds.u1[lane] = Ub[ju * NU + lane];
-            }
+            loadSegment<NX, NU>(lds.seg, lane, Xb, Ub, i, ju);
             if (g < NU && col < NX)
             {
                 lds.G0[g * RT + col] = Gb[(i * NU + g) * NX + col];
@@ -128,63 +141,12 @@ __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int
             }
             WAVE_SYNC();
             for (int n = 0; n < steps; n++)
-            {
-                d4_t kk[RK_S];
-#pragma unroll
-                for (int s = 0; s < RK_S; s++)
-                {
+                rkf78TileStep(Sc, h, [&](int s, const d4_t Ss) __attribute__((always_inline)) {
                     const double a = (double(n) + RK_C[s]) / double(steps);
-                    if (lane < NX)
-                    {
-                        double x[NX], u[NU], uaux[JR::NUAUX > 0 ? JR::NUAUX : 1], jr[NX + NU];
-#pragma unroll
-                        for (int j = 0; j < NX; j++)
-                            x[j] = lds.x0[j] + a * (lds.x1[j] - lds.x0[j]);
-#pragma unroll
-                        for (int j = 0; j < NU; j++)
-                            u[j] = lds.u0[j] + a * (lds.u1[j] - lds.u0[j]);
-                        JR::prepareInput(u, p, uaux);
-                        (void)JR::row(lane, x, u, p, aux, uaux, jr);
-#pragma unroll
-                        for (int c = 0; c < NX; c++)
-                        {
-                            double acl = jr[c];
-#pragma unroll
-                            for (int q = 0; q < NU; q++)
-                                acl -= jr[NX + q] * (lds.G0[q * RT + c] + a * (lds.G1[q * RT + c] - lds.G0[q * RT + c]));
-                            lds.At[c * RT + lane] = acl;
-                        }
-                    }
-                    WAVE_SYNC();
                     double Ac[4];
-#pragma unroll
-                    for (int c = 0; c < 4; c++)
-                        Ac[c] = lds.At[(4 * c + g) * RT + col];
-                    WAVE_SYNC();
-                    d4_t Ss;
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                    {
-                        double acc = 0.;
-#pragma unroll
-                        for (int qq = 0; qq < s; qq++)
-                            if (RK_A[s][qq] != 0.)
-                                acc += RK_A[s][qq] * kk[qq][r];
-                        Ss[r] = Sc[r] + h * acc;
-                    }
-                    kk[s] = covarianceRhs(Ss, Ac, wd);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                {
-                    double acc = 0.;
-#pragma unroll
-                    for (int s = 0; s < RK_S; s++)
-                        if (RK_B[s] != 0.)
-                            acc += RK_B[s] * kk[s][r];
-                    Sc[r] += h * acc;
-                }
-            }
+                    closedLoopJacobian<P>(lds, lane, a, p, aux, Ac);
+                    return covarianceRhs(Ss, Ac, wd);
+                });
         }
         // ---- node k: S(t_k), its standard deviations and the input covariance G[k] S G[k]' = G (S G')  (8 matrix-core instructions) ----
         double Gt[4]; // the lane's share of the gain tile (rows >= nu zero): G[col][4c + g]
@@ -210,18 +172,12 @@ __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int
             kfail = k;
             break;
         }
+        if (cvb)
+            storeTile<NX>(lane, cvb + k * NX * NX, Sc);
 #pragma unroll
         for (int r = 0; r < 4; r++)
-        {
-            const int row = 4 * r + g;
-            if (row < NX && col < NX)
-            {
-                if (cvb)
-                    cvb[(k * NX + row) * NX + col] = Sc[r];
-                if (row == col)
-                    sdb[k * NX + col] = sqrt(Sc[r] > 0. ? Sc[r] : 0.); // a diagonal entry negative from rounding: 0
-            }
-        }
+            if (4 * r + g == col && col < NX)
+                sdb[k * NX + col] = sqrt(Sc[r] > 0. ? Sc[r] : 0.); // a diagonal entry negative from rounding: 0
         if (g < NU && col < NU)
             icb[(k * NU + g) * NU + col] = Sk[0];
     }
@@ -233,10 +189,8 @@ __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int
     if (cvb)
         for (int e = kfail * NX * NX + lane; e < K * NX * NX; e += WAVE)
             cvb[e] = 0.;
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-        if (4 * r + g < NX && col < NX)
-            fcb[(4 * r + g) * NX + col] = kfail == K ? Sc[r] : 0.;
+    const d4_t zero = {0., 0., 0., 0.};
+    storeTile<NX>(lane, fcb, kfail == K ? Sc : zero);
     if (lane == 0)
         status[b] = kfail < K ? ST_NONFINITE : (incomplete ? ST_GAINS_INCOMPLETE : ST_OK);
 }

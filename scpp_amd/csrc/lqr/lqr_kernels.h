@@ -70,6 +70,8 @@ struct LqrPluginList
 };
 using LqrPlugins = LqrPluginList<RocketQuatLqr, Rocket2dLqr, Lander3dofLqr>;
 
+__device__ __forceinline__ bool isFinite(double v) { return fabs(v) <= 1.7976931348623157e308; } // false for a NaN
+
 // ---- reductions over the 32 lanes of one problem: symmetric xor butterflies, so every lane of the half holds the bitwise identical result ----
 __device__ __forceinline__ double halfSum(double v)
 {
@@ -114,7 +116,7 @@ __device__ __forceinline__ bool gaussJordan(double (&W)[N], int nrows, int r, in
             }
         }
         piv[j] = bi;
-        if (!(bv > 0.) || !(bv <= 1.7976931348623157e308))
+        if (!(bv > 0.) || !isFinite(bv))
             ok = false;
         double prow[N];
 #pragma unroll
@@ -331,7 +333,7 @@ __global__ void __launch_bounds__(WAVE) lqr_gain_kernel(long nodes, int K, int n
         a2 = halfSum(a2);
         b2 = halfSum(b2);
         it++;
-        if (!ok || !(d2 <= 1.7976931348623157e308) || !(a2 <= 1.7976931348623157e308))
+        if (!ok || !isFinite(d2) || !isFinite(a2))
         {
             st = ST_NONFINITE;
             break;
@@ -390,7 +392,7 @@ __global__ void __launch_bounds__(WAVE) lqr_gain_kernel(long nodes, int K, int n
     }
     if (r < NX)
         for (int a = 0; a < NU; a++)
-            if (!(fabs(kout[a]) <= 1.7976931348623157e308))
+            if (!isFinite(kout[a]))
                 bad = 1;
     bad = halfOr(bad);
     if (bad && st == ST_OK)
@@ -437,13 +439,13 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, i
     {
         y[j] = x_start[b * NX + j];
         xf[j] = x_final[j];
-        finite = finite && (fabs(y[j]) <= 1.7976931348623157e308);
+        finite = finite && isFinite(y[j]);
         e0 += (y[j] - xf[j]) * (y[j] - xf[j]);
     }
     for (int j = 0; j < NU; j++)
         u[j] = 0.;
     const double t_max = T[b];
-    finite = finite && (fabs(t_max) <= 1.7976931348623157e308);
+    finite = finite && isFinite(t_max);
     const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU, *Gb = G + b * K * NU * NX;
     double t = 0., max_dev = 0.;
     int steps = 0, st = ST_OK, nrec = 0;
@@ -492,7 +494,7 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, i
         }
         bool ufin = true;
         for (int c = 0; c < NU; c++)
-            ufin = ufin && (fabs(un[c]) <= 1.7976931348623157e308);
+            ufin = ufin && isFinite(un[c]);
         if (!ufin)
         {
             st = ST_NONFINITE; // a non-finite reference node, input or gain (a failed solver instance): the last applied input is kept
@@ -533,7 +535,7 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, i
         }
         bool fin = true;
         for (int j = 0; j < NX; j++)
-            fin = fin && (fabs(yn[j]) <= 1.7976931348623157e308);
+            fin = fin && isFinite(yn[j]);
         if (!fin)
         {
             st = ST_NONFINITE; // keeps the last finite state

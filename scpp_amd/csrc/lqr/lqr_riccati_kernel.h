@@ -3,10 +3,8 @@
 //
 //   -dP/dt = A(t)'P + P A(t) - P B(t) R^-1 B(t)'P + Q,   P(T) = Qf,   K_k = R^-1 B_k' P(t_k)
 //
-// Mapping: ONE WAVEFRONT PER TRAJECTORY.  nx <= 14, so P, padded with zeros, is one 16 x 16 FP64 tile, kept in the accumulator layout of
-// v_mfma_f64_16x16x4_f64 (lane l, register r: row (l >> 4) + 4 r, column l & 15): 4 doubles per lane for P and for each of the 13 RKF78 stage
-// slopes.  In that layout register c of lane l is at once the lane's share of chunk c of the B operand (P[4c + g][col]) and, P being symmetric, of
-// the A operand (P[col][4c + g]), and the same holds for the Jacobian tile read back from LDS.  A right-hand side is therefore thirteen
+// Mapping: ONE WAVEFRONT PER TRAJECTORY, P one 16 x 16 FP64 tile in the accumulator layout (lqr_tile_sweep.h: register c of a lane is its share of
+// the A operand and of the B operand alike, for P and for the Jacobian tile read back from LDS).  A right-hand side is therefore thirteen
 // matrix-core instructions and no lane exchange:
 //     M1 = P A        4   (A operand: P, B operand: A)
 //     M2 = A'P        4   (A operand: A, B operand: P)        M2[i][j] is bitwise M1[j][i]: the same products, summed in the same order
@@ -16,45 +14,31 @@
 // P STAYS SYMMETRIC BY CONSTRUCTION (bitwise: F[i][j] and F[j][i] are the same operations on the same numbers); nothing is symmetrised.
 // The Jacobian rows are the generated rows the gain kernel evaluates: lane r < nx evaluates row r at the interpolated reference and writes it to LDS.
 #pragma once
-#include "lqr_kernels.h"
+#include "lqr_tile_sweep.h"
 
 namespace scpp
 {
 namespace lqr
 {
 
-constexpr int RT = 16; // tile edge
-
 struct RiccatiLds
 {
     double A[RT * RT]; // rows and columns >= nx stay zero
     double Bm[RT * 4]; // rows >= nx, columns >= nu stay zero
-    double x0[RT], x1[RT], u0[4], u1[4];
+    SegmentLds seg;
 };
-
-__device__ __forceinline__ int waveOr(int v)
-{
-    for (int m = WAVE / 2; m >= 1; m >>= 1)
-        v |= __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ bool isFinite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 // lane r < NX: row r of [A | B] at (x, u) -> LDS; afterwards every lane holds its share of both tiles
 template <class P>
 __device__ __forceinline__ void riccatiJacobian(RiccatiLds &lds, int lane, const double *x, const double *u, const double *p, const double *aux,
                                                 double (&At)[4], double (&Bt)[4])
 {
-    using Model = typename P::Model;
-    using JR = typename Model::JacobianRows;
-    constexpr int NX = Model::NX, NU = Model::NU;
+    constexpr int NX = P::Model::NX, NU = P::Model::NU;
     const int g = lane >> 4, col = lane & 15;
     if (lane < NX)
     {
-        double uaux[JR::NUAUX > 0 ? JR::NUAUX : 1], jr[NX + NU];
-        JR::prepareInput(u, p, uaux);
-        (void)JR::row(lane, x, u, p, aux, uaux, jr);
+        double jr[NX + NU];
+        jacobianRow<P>(lane, x, u, p, aux, jr);
 #pragma unroll
         for (int c = 0; c < NX; c++)
             lds.A[lane * RT + c] = jr[c];
@@ -127,21 +111,10 @@ __global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uR
         p[j] = par[b * par_stride + j];
     JR::prepare(p, aux);
     const double rinv = g < NU ? 1. / rw[g < NU ? g : 0] : 0., sr = sqrt(rinv);
-    d4_t qd, Pc;
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-    {
-        const bool diag = (4 * r + g == col) && col < NX;
-        qd[r] = diag ? qw[diag ? col : 0] : 0.;
-        Pc[r] = diag ? qfw[diag ? col : 0] : 0.;
-    }
+    const d4_t qd = diagonalTile<NX>(lane, qw);
+    d4_t Pc = diagonalTile<NX>(lane, qfw);
     const double t_max = T[b];
-    int bad = isFinite(t_max) ? 0 : 1;
-    for (int e = lane; e < K * NX; e += WAVE)
-        bad |= isFinite(Xb[e]) ? 0 : 1;
-    for (int e = lane; e < nU * NU; e += WAVE)
-        bad |= isFinite(Ub[e]) ? 0 : 1;
-    bad = waveOr(bad);
+    const int bad = waveOr(referenceNonFinite<NX, NU>(lane, t_max, Xb, Ub, K, nU));
     WAVE_SYNC();
 
     const double h = t_max / double(K - 1) / double(steps);
@@ -151,60 +124,17 @@ __global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uR
         if (k < K - 1)
         {
             // ---- segment k: P(t_{k+1}) -> P(t_k), `steps` RKF78 steps ----
-            const int ju = foh ? k + 1 : k;
-            if (lane < NX)
-            {
-                lds.x0[lane] = Xb[k * NX + lane];
-                lds.x1[lane] = Xb[(k + 1) * NX + lane];
-            }
-            if (lane < NU)
-            {
-                lds.u0[lane] = Ub[k * NU + lane];
-                lds.u1[lane] = Ub[ju * NU + lane];
-            }
+            loadSegment<NX, NU>(lds.seg, lane, Xb, Ub, k, foh ? k + 1 : k);
             WAVE_SYNC();
             for (int n = 0; n < steps; n++)
-            {
-                d4_t kk[RK_S];
-#pragma unroll
-                for (int s = 0; s < RK_S; s++)
-                {
+                rkf78TileStep(Pc, h, [&](int s, const d4_t Ps) __attribute__((always_inline)) {
                     const double a = 1. - (double(n) + RK_C[s]) / double(steps);
                     double x[NX], u[NU], At[4], Bt[4];
                     if (lane < NX)
-                    {
-#pragma unroll
-                        for (int j = 0; j < NX; j++)
-                            x[j] = lds.x0[j] + a * (lds.x1[j] - lds.x0[j]);
-#pragma unroll
-                        for (int j = 0; j < NU; j++)
-                            u[j] = lds.u0[j] + a * (lds.u1[j] - lds.u0[j]);
-                    }
+                        interpolateSegment(lds.seg, a, x, u);
                     riccatiJacobian<P>(lds, lane, x, u, p, aux, At, Bt);
-                    d4_t Ps;
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                    {
-                        double acc = 0.;
-#pragma unroll
-                        for (int qq = 0; qq < s; qq++)
-                            if (RK_A[s][qq] != 0.)
-                                acc += RK_A[s][qq] * kk[qq][r];
-                        Ps[r] = Pc[r] + h * acc;
-                    }
-                    kk[s] = riccatiRhs(Ps, At, Bt, sr, qd);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                {
-                    double acc = 0.;
-#pragma unroll
-                    for (int s = 0; s < RK_S; s++)
-                        if (RK_B[s] != 0.)
-                            acc += RK_B[s] * kk[s][r];
-                    Pc[r] += h * acc;
-                }
-            }
+                    return riccatiRhs(Ps, At, Bt, sr, qd);
+                });
         }
         // ---- node k: K_k = R^-1 B_k'P(t_k), B_k at (X[k], U[min(k, nU-1)]): the frozen-time kernel's linearisation point ----
         double x[NX], u[NU], At[4], Bt[4];
@@ -236,12 +166,7 @@ __global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uR
         if (g < NU && col < NX)
             Gb[(k * NU + g) * NX + col] = gain;
         if (Pb)
-        {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (4 * r + g < NX && col < NX)
-                    Pb[(k * NX + 4 * r + g) * NX + col] = Pc[r];
-        }
+            storeTile<NX>(lane, Pb + k * NX * NX, Pc);
         if (lane == 0)
         {
             status[b * K + k] = ST_OK;

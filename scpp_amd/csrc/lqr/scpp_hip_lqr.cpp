@@ -1,4 +1,4 @@
-// C ABI of the batched LQR tracker (include/scpp_hip_lqr.h): context, buffers and launches for csrc/lqr/lqr_kernels.h.
+// C ABI of the batched LQR tracker (include/scpp_hip_lqr.h): context, buffers and launches for the kernels of csrc/lqr/.
 // Built as a library of its own (libscpp_lqr.so; with -DSCPP_HIP_EMU: the CPU emulation of the same source), see DESIGN.md 4.8.
 #include "../../../include/scpp_hip_lqr.h"
 #include "lqr_kernels.h"
@@ -107,6 +107,68 @@ static bool allFinite(const double *v, size_t n)
         if (!std::isfinite(v[i]))
             return false;
     return true;
+}
+
+// whatever changes the trajectories or replaces the gains: no gains, no P, no covariance
+static void invalidateGains(scpp_hip_lqr_ctx *c) { c->have_gains = c->gains_computed = c->have_p = c->have_cov = false; }
+
+// a change of weights or parameters: gains the library computed are stale, gains the caller supplied (scpp_hip_lqr_set_gains) stay
+static void invalidateComputedGains(scpp_hip_lqr_ctx *c)
+{
+    if (c->gains_computed)
+        invalidateGains(c);
+}
+
+// what every launch needs: trajectories, and parameter rows for one or for that number of trajectories
+static int readyToLaunch(const scpp_hip_lqr_ctx *c)
+{
+    return c->have_traj && c->have_par && (c->par_rows == 1 || c->par_rows == c->B) ? SCPP_OK : SCPP_E_STATE;
+}
+
+// launch(Plugin{}) enqueues the kernel of the context's model
+template <class F>
+static int launchKernel(scpp_hip_lqr_ctx *c, F &&launch)
+{
+    const int rc = withLqrPlugin(c->model, [&](auto pl) {
+        launch(pl);
+        return 0;
+    });
+    if (rc)
+        return rc;
+    return hipGetLastError() == hipSuccess ? SCPP_OK : SCPP_E_HIP;
+}
+
+// *n_ok = the entries of the device array `status` [n] equal to SCPP_LQR_OK (n_ok == nullptr: nothing is downloaded)
+static int countOk(scpp_hip_lqr_ctx *c, const int *status, size_t n, int *n_ok)
+{
+    if (!n_ok)
+        return SCPP_OK;
+    HostBuf<int> st(n);
+    if (!st.p)
+        return SCPP_E_HIP;
+    CHECK_HIP(hipMemcpyAsync(st.p, status, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    int ok = 0;
+    for (size_t i = 0; i < n; i++)
+        ok += (st.p[i] == SCPP_LQR_OK);
+    *n_ok = ok;
+    return SCPP_OK;
+}
+
+// *buf holds at least `need` doubles afterwards; on failure *buf == nullptr and *cap == 0
+static int growTo(scpp_hip_lqr_ctx *c, double **buf, size_t *cap, size_t need)
+{
+    if (need <= *cap)
+        return SCPP_OK;
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    if (*buf)
+        (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    if (devAlloc(buf, need))
+        return SCPP_E_HIP;
+    *cap = need;
+    return SCPP_OK;
 }
 
 extern "C"
@@ -236,8 +298,7 @@ int scpp_hip_lqr_set_weights(scpp_hip_lqr_ctx *c, const double *q, const double 
     CHECK_HIP(hipMemcpyAsync(c->q, q, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipMemcpyAsync(c->r, r, size_t(c->nu) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
-    if (c->gains_computed)
-        c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
+    invalidateComputedGains(c);
     return SCPP_OK;
 }
 
@@ -252,8 +313,7 @@ int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
     c->par_rows = B;
     c->have_par = true;
     c->have_cov = false;
-    if (c->gains_computed)
-        c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
+    invalidateComputedGains(c);
     return SCPP_OK;
 }
 
@@ -272,7 +332,7 @@ int scpp_hip_lqr_set_trajectories(scpp_hip_lqr_ctx *c, const double *X, const do
     c->uRows = c->nU;
     c->B = B;
     c->have_traj = true;
-    c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
+    invalidateGains(c);
     return SCPP_OK;
 }
 
@@ -286,7 +346,7 @@ int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *c, const void *dX, co
     c->uRows = u_rows;
     c->B = B;
     c->have_traj = true;
-    c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
+    invalidateGains(c);
     return SCPP_OK;
 }
 
@@ -294,38 +354,21 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
 {
     if (!c)
         return SCPP_E_ARG;
-    if (!c->have_traj || !c->have_par)
-        return SCPP_E_STATE;
-    if (c->par_rows != 1 && c->par_rows != c->B)
-        return SCPP_E_STATE; // parameter rows for another number of trajectories
+    if (int rc = readyToLaunch(c))
+        return rc;
     DeviceGuard guard(c->device);
     const long nodes = long(c->B) * c->K;
     const unsigned grid = unsigned((nodes + 1) / 2);
-    int rc = withLqrPlugin(c->model, [&](auto pl) {
+    int rc = launchKernel(c, [&](auto pl) {
         using P = decltype(pl);
         hipLaunchKernelGGL((lqr_gain_kernel<P>), dim3(grid), dim3(WAVE), 0, c->stream, nodes, c->K, c->nU, c->uRows, c->tX, c->tU,
                            (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r, c->G, c->gstatus, c->giters);
-        return 0;
     });
     if (rc)
         return rc;
-    if (hipGetLastError() != hipSuccess)
-        return SCPP_E_HIP;
     c->have_gains = c->gains_computed = true;
     c->have_p = c->have_cov = false;
-    if (n_ok)
-    {
-        HostBuf<int> st(static_cast<size_t>(nodes));
-        if (!st.p)
-            return SCPP_E_HIP;
-        CHECK_HIP(hipMemcpyAsync(st.p, c->gstatus, size_t(nodes) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        CHECK_HIP(hipStreamSynchronize(c->stream));
-        int n = 0;
-        for (long i = 0; i < nodes; i++)
-            n += (st.p[i] == SCPP_LQR_OK);
-        *n_ok = n;
-    }
-    return SCPP_OK;
+    return countOk(c, c->gstatus, size_t(nodes), n_ok);
 }
 
 int scpp_hip_lqr_set_terminal_weights(scpp_hip_lqr_ctx *c, const double *qf)
@@ -342,8 +385,7 @@ int scpp_hip_lqr_set_terminal_weights(scpp_hip_lqr_ctx *c, const double *qf)
         CHECK_HIP(hipStreamSynchronize(c->stream));
     }
     c->have_qf = qf != nullptr;
-    if (c->gains_computed)
-        c->have_gains = c->gains_computed = c->have_p = c->have_cov = false;
+    invalidateComputedGains(c);
     return SCPP_OK;
 }
 
@@ -351,54 +393,29 @@ int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *c, int steps, int keep_
 {
     if (!c || steps < 1)
         return SCPP_E_ARG;
-    if (!c->have_traj || !c->have_par)
-        return SCPP_E_STATE;
-    if (c->par_rows != 1 && c->par_rows != c->B)
-        return SCPP_E_STATE;
+    if (int rc = readyToLaunch(c))
+        return rc;
     if (long(c->K - 1) * steps > 0x7fffffffL)
         return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
     DeviceGuard guard(c->device);
     const long nodes = long(c->B) * c->K;
     const size_t p_need = size_t(nodes) * c->nx * c->nx;
     c->have_p = false;
-    if (keep_p && p_need > c->P_cap)
-    {
-        CHECK_HIP(hipStreamSynchronize(c->stream));
-        if (c->P)
-            (void)hipFree(c->P);
-        c->P = nullptr;
-        c->P_cap = 0;
-        if (devAlloc(&c->P, p_need))
-            return SCPP_E_HIP;
-        c->P_cap = p_need;
-    }
-    int rc = withLqrPlugin(c->model, [&](auto pl) {
+    if (keep_p)
+        if (int rc = growTo(c, &c->P, &c->P_cap, p_need))
+            return rc;
+    int rc = launchKernel(c, [&](auto pl) {
         using P = decltype(pl);
         hipLaunchKernelGGL((lqr_riccati_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
                            (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
                            (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep_p ? c->P : (double *)nullptr);
-        return 0;
     });
     if (rc)
         return rc;
-    if (hipGetLastError() != hipSuccess)
-        return SCPP_E_HIP;
     c->have_gains = c->gains_computed = true;
     c->have_p = keep_p != 0;
     c->have_cov = false;
-    if (n_ok)
-    {
-        HostBuf<int> st(static_cast<size_t>(nodes));
-        if (!st.p)
-            return SCPP_E_HIP;
-        CHECK_HIP(hipMemcpyAsync(st.p, c->gstatus, size_t(nodes) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        CHECK_HIP(hipStreamSynchronize(c->stream));
-        int n = 0;
-        for (long i = 0; i < nodes; i++)
-            n += (st.p[i] == SCPP_LQR_OK);
-        *n_ok = n;
-    }
-    return SCPP_OK;
+    return countOk(c, c->gstatus, size_t(nodes), n_ok);
 }
 
 int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *c, double *P)
@@ -445,8 +462,8 @@ int scpp_hip_lqr_set_gains(scpp_hip_lqr_ctx *c, const double *gains)
     DeviceGuard guard(c->device);
     CHECK_HIP(hipMemcpyAsync(c->G, gains, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream));
+    invalidateGains(c);
     c->have_gains = true;
-    c->gains_computed = c->have_p = c->have_cov = false;
     return SCPP_OK;
 }
 
@@ -503,51 +520,28 @@ int scpp_hip_lqr_propagate_covariance(scpp_hip_lqr_ctx *c, int steps, int keep_c
 {
     if (!c || steps < 1)
         return SCPP_E_ARG;
-    if (!c->have_traj || !c->have_par || !c->have_gains || !c->have_cov_in)
-        return SCPP_E_STATE;
-    if ((c->par_rows != 1 && c->par_rows != c->B) || (c->s0_rows != 1 && c->s0_rows != c->B))
-        return SCPP_E_STATE; // rows for another number of trajectories
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B))
+        return SCPP_E_STATE; // no gains, no initial covariance, or one for another number of trajectories
     DeviceGuard guard(c->device);
     const size_t need = size_t(c->B) * c->K * c->nx * c->nx;
     c->have_cov = false;
-    if (keep_cov && need > c->cov_cap)
-    {
-        CHECK_HIP(hipStreamSynchronize(c->stream));
-        if (c->cov)
-            (void)hipFree(c->cov);
-        c->cov = nullptr;
-        c->cov_cap = 0;
-        if (devAlloc(&c->cov, need))
-            return SCPP_E_HIP;
-        c->cov_cap = need;
-    }
-    int rc = withLqrPlugin(c->model, [&](auto pl) {
+    if (keep_cov)
+        if (int rc = growTo(c, &c->cov, &c->cov_cap, need))
+            return rc;
+    int rc = launchKernel(c, [&](auto pl) {
         using P = decltype(pl);
         hipLaunchKernelGGL((lqr_covariance_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
                            (const double *)c->par, c->par_stride, (const double *)c->G, (const int *)(c->gains_computed ? c->gstatus : nullptr),
                            (const double *)c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, (const double *)c->cw, c->cstd, c->cin, c->cfin, c->cstatus,
                            keep_cov ? c->cov : (double *)nullptr);
-        return 0;
     });
     if (rc)
         return rc;
-    if (hipGetLastError() != hipSuccess)
-        return SCPP_E_HIP;
     c->have_cov = true;
     c->cov_kept = keep_cov != 0;
-    if (n_ok)
-    {
-        HostBuf<int> st(static_cast<size_t>(c->B));
-        if (!st.p)
-            return SCPP_E_HIP;
-        CHECK_HIP(hipMemcpyAsync(st.p, c->cstatus, size_t(c->B) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        CHECK_HIP(hipStreamSynchronize(c->stream));
-        int n = 0;
-        for (int b = 0; b < c->B; b++)
-            n += (st.p[b] == SCPP_LQR_OK);
-        *n_ok = n;
-    }
-    return SCPP_OK;
+    return countOk(c, c->cstatus, size_t(c->B), n_ok);
 }
 
 int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *c, double *state_std, double *input_cov, double *final_cov, int *status, double *cov)
@@ -586,9 +580,9 @@ int scpp_hip_lqr_track(scpp_hip_lqr_ctx *c, const double *x_start, const double 
     if (!c || !x_start || !x_final || B < 1 || !(time_step > 0.) || !std::isfinite(time_step) || substeps < 1 || max_steps < 1 ||
         n_record < 0 || n_record > B || (n_record > 0 && write_steps < 1))
         return SCPP_E_ARG;
-    if (!c->have_traj || !c->have_par || !c->have_gains)
-        return SCPP_E_STATE;
-    if (c->par_rows != 1 && c->par_rows != c->B)
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (!c->have_gains)
         return SCPP_E_STATE;
     if (B != c->B)
         return SCPP_E_ARG; // one start per trajectory
@@ -618,17 +612,14 @@ int scpp_hip_lqr_track(scpp_hip_lqr_ctx *c, const double *x_start, const double 
     CHECK_HIP(hipMemcpyAsync(c->xs, x_start, size_t(B) * c->nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipMemcpyAsync(c->xf, x_final, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned grid = unsigned((B + WAVE - 1) / WAVE);
-    int rc = withLqrPlugin(c->model, [&](auto pl) {
+    int rc = launchKernel(c, [&](auto pl) {
         using P = decltype(pl);
         hipLaunchKernelGGL((lqr_track_kernel<P>), dim3(grid), dim3(WAVE), 0, c->stream, B, c->K, c->nU, c->uRows, c->tX, c->tU, c->tT,
                            (const double *)c->par, c->par_stride, (const double *)c->G, (const double *)c->xs, (const double *)c->xf, time_step,
                            substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn);
-        return 0;
     });
     if (rc)
         return rc;
-    if (hipGetLastError() != hipSuccess)
-        return SCPP_E_HIP;
     CHECK_HIP(hipStreamSynchronize(c->stream)); // x_start / x_final are the caller's
     c->have_track = true;
     c->track_B = B;
