@@ -11,7 +11,10 @@
  *   the closed loop of SC_tracking        scpp/src/SC_tracking.cpp:48-75          scpp_hip_lqr_track
  *       scpp::simulate (RKF78, fixed steps)   scpp_core/src/simulation.cpp:25-42
  *   LQRAlgorithm::initialize / solve, the loop of LQR_sim   LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82   the same, see scpp_hip_lqr_set_stop_tolerance
- *       (without LQR_sim's input clipping, which addresses u.z() of a two-input model and does not compile for Rocket2D)
+ *       LQR_sim's input clipping (LQR_sim.cpp:55-66)                                          scpp_hip_lqr_set_input_limits: the same three
+ *       steps in the same order for the models whose input is a thrust vector; the reference's code addresses u.z() of the two-input
+ *       Rocket2D, the only model it builds LQR_sim for, and does not compile: Rocket2D gets the box of rocket2d.cpp:77-83 instead
+ *   nothing: the reference flies one start per trajectory                                     scpp_hip_lqr_track_samples
  *   nothing: the reference has no finite-horizon controller                                   scpp_hip_lqr_set_terminal_weights,
  *       (the differential Riccati equation along the trajectory)               scpp_hip_lqr_compute_gains_riccati, _download_riccati
  *   nothing: the reference has no covariance analysis                                         scpp_hip_lqr_set_covariance_inputs,
@@ -43,6 +46,18 @@
  *     segment; stage s of step n sits at a = (n + c_s) / steps.  Node k records S(t_k) and the input covariance G[k] S(t_k) G[k]' with the
  *     node's own gain; node 0 records S0 exactly.  S is kept symmetric BY CONSTRUCTION (A_cl S and S A_cl' are both formed, from the same
  *     products in the same order); it is never symmetrised, which is why S0 has to be symmetric to the bit.
+ *
+ *   - input limits (scpp_hip_lqr_set_input_limits) are an addition to the tracking loop, off by default: with limits (T_min, T_max, angle_max)
+ *     the loop applies u = sat(u_cmd), u_cmd = -K_t (x - x_ref) + u_ref computed as without them.  A non-finite u_cmd retires the flight with
+ *     status -2 before sat.  Thrust-vector models (RocketQuat: u = (T_B, tau_z), sat acts on u[0..2] and u[3] passes through; Lander3dof:
+ *     u = T_I), in this order:  1. u_z = max(T_min, u_z);  2. c = tan(angle_max) u_z, and if |u_xy| > c then u_xy *= c / |u_xy|;
+ *     3. if |u| > T_max then u *= T_max / |u|.  With T_min <= T_max cos(angle_max), which the host demands, the result lies in the input set of
+ *     the models' constraint tables (u_z >= T_min, |u_xy| <= tan(angle_max) u_z, |u| <= T_max); without it step 3 could undo step 1.
+ *     Rocket2D (u = (gimbal, thrust)): gimbal clamped to [-angle_max, angle_max], thrust to [T_min, T_max].  A point inside the set is returned
+ *     bitwise.  It is a clip: the gains do not know about it and there is no anti-windup.  Per flight: n_sat = the plant steps on which
+ *     u != u_cmd in any component, max_clip = the largest |u_cmd - u|_2 met; out_u and the record hold the applied input u.
+ *   - scpp_hip_lqr_track_samples flies `samples` starts per trajectory: flight f of F = B samples follows trajectory f / samples (its X, U, t,
+ *     gains, parameter row and limits row) from x_start[f]; trajectories and gains are neither copied nor recomputed.
  *
  * Conventions as in scpp_hip.h: every function returns 0 or a negative SCPP_E_* code, nothing throws; host buffers are caller-owned, float64
  * (int32 where said), C-contiguous; one host thread per context.  All work goes on the context's own stream; nothing synchronises the device.
@@ -131,11 +146,25 @@ extern "C"
        caller sets a constant two-node "trajectory" (X = x_final, U = u_eq, t = sim_time) and the one gain of the operating point
        (scpp_hip_lqr_set_gains), so that u = -K (x - x_final) + u_eq; the same two kernels, no third.  0 (the default) switches it off. */
     int scpp_hip_lqr_set_stop_tolerance(scpp_hip_lqr_ctx *ctx, double stop_tol);
+    /* input limits of the tracking loop, SI units: lim [B][3] = (T_min, T_max, angle_max in radians) per trajectory; B == 1 broadcasts one
+       row, otherwise B must equal the number of trajectories: scpp_hip_lqr_track / _track_samples return SCPP_E_STATE when it does not.
+       NULL (the default) switches limits off.  SCPP_E_ARG for a non-finite entry, T_min < 0, T_max <= T_min, angle_max outside (0, pi/2),
+       and, for the thrust-vector models, T_min > T_max cos(angle_max).  The limits stay until they are set again (new trajectories do not
+       clear them); they invalidate neither gains nor a covariance sweep, which describe the unlimited linear loop. */
+    int scpp_hip_lqr_set_input_limits(scpp_hip_lqr_ctx *ctx, const double *lim /* [B or 1][3] or NULL */, int B);
     /* B closed loops from x_start [B][nx] towards x_final [nx] along the trajectories: time_step > 0 (reference: 0.01), substeps >= 1 RKF78
        steps per plant step (reference: 20), at most max_steps >= 1 plant steps; the first n_record instances record every write_steps-th
        step.  *n_finite (optional) = loops that did not retire non-finite. */
     int scpp_hip_lqr_track(scpp_hip_lqr_ctx *ctx, const double *x_start, const double *x_final, int B, double time_step, int substeps,
                            int max_steps, int n_record, int write_steps, int *n_finite);
+    /* F = B samples closed loops, `samples` >= 1 (SCPP_E_ARG otherwise) per trajectory, flight f along trajectory f / samples from
+       x_start[f]; B is the number of trajectories.  Everything else as scpp_hip_lqr_track, which is this call with samples = 1; n_record
+       counts flights (n_record <= F).  The downloads below then return F rows.  The per-flight buffers grow on demand. */
+    int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *ctx, const double *x_start /* [B*samples][nx] */, const double *x_final, int B, int samples,
+                                   double time_step, int substeps, int max_steps, int n_record, int write_steps, int *n_finite);
+    /* n_sat [F] int32, max_clip [F] of the last flights (zeros when they flew without limits); either pointer may be NULL.  SCPP_E_STATE
+       before any flight. */
+    int scpp_hip_lqr_track_download_saturation(scpp_hip_lqr_ctx *ctx, int *n_sat /* [F] */, double *max_clip /* [F] */);
     /* x [B][nx], u [B][nu] (last input), t [B], steps [B] int32, status [B] int32, err0 / err1 [B] = |x - x_final| at start / end,
        max_dev [B] = largest |x - x_ref| met; any pointer may be NULL */
     int scpp_hip_lqr_track_download(scpp_hip_lqr_ctx *ctx, double *x, double *u, double *t, int *steps, int *status, double *err0,

@@ -27,4 +27,5 @@ from .scvx_algorithm import SCvxAlgorithm, load_scvx_opts  # noqa: F401
 from .mpc_algorithm import MPCAlgorithm, MPCSim  # noqa: F401
 from ._lib import MpcOpts  # noqa: F401
 from ._lib import LqrContext, load_lqr_library  # noqa: F401
-from .lqr import LQRAlgorithm, LQRSim, LQRTracker, load_lqr_covariance_inputs, load_lqr_terminal_weights, load_lqr_weights  # noqa: F401
+from .lqr import (LQRAlgorithm, LQRSim, LQRTracker, load_lqr_covariance_inputs, load_lqr_terminal_weights, load_lqr_weights,  # noqa: F401
+                  model_input_limits)

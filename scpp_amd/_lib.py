@@ -484,6 +484,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_track_record_size", "scpp_hip_lqr_track_record", "scpp_hip_lqr_synchronize",
     "scpp_hip_lqr_set_terminal_weights", "scpp_hip_lqr_compute_gains_riccati", "scpp_hip_lqr_download_riccati",
     "scpp_hip_lqr_set_covariance_inputs", "scpp_hip_lqr_propagate_covariance", "scpp_hip_lqr_download_covariance",
+    "scpp_hip_lqr_set_input_limits", "scpp_hip_lqr_track_samples", "scpp_hip_lqr_track_download_saturation",
 ]
 _lqr_libs = {}
 
@@ -506,6 +507,8 @@ def load_lqr_library(path=None):
             raise ScppHipError(f"{path} does not export {s}")
     lib.scpp_hip_lqr_version.restype = C.c_char_p
     lib.scpp_hip_lqr_track.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.scpp_hip_lqr_track_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_void_p]
     lib.scpp_hip_lqr_set_trajectories_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     _lqr_libs[path] = lib
     return lib
@@ -619,6 +622,15 @@ class LqrContext:
     def set_stop_tolerance(self, stop_tol):
         _chk(self.lib.scpp_hip_lqr_set_stop_tolerance(self.h, C.c_double(stop_tol)), "lqr_set_stop_tolerance")
 
+    def set_input_limits(self, lim=None):
+        """lim [B or 1][3] = (T_min, T_max, angle_max in radians) in SI units, one row for all trajectories or one per trajectory; None
+        switches the limits off"""
+        if lim is None:
+            _chk(self.lib.scpp_hip_lqr_set_input_limits(self.h, None, 0), "lqr_set_input_limits")
+            return
+        lim = np.ascontiguousarray(lim, dtype=np.float64).reshape(-1, 3)
+        _chk(self.lib.scpp_hip_lqr_set_input_limits(self.h, _p(lim), int(lim.shape[0])), "lqr_set_input_limits")
+
     def track(self, x_start, x_final, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30):
         x_start = np.ascontiguousarray(x_start, dtype=np.float64).reshape(-1, self.nx)
         x_final = np.ascontiguousarray(x_final, dtype=np.float64).reshape(self.nx)
@@ -627,6 +639,26 @@ class LqrContext:
                                          int(max_steps), int(n_record), int(write_steps), C.byref(n)), "lqr_track")
         self.track_B = x_start.shape[0]
         return int(n.value)
+
+    def track_samples(self, x_start, x_final, samples=1, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30):
+        """x_start [B * samples][nx]: flight f follows trajectory f // samples"""
+        x_start = np.ascontiguousarray(x_start, dtype=np.float64).reshape(-1, self.nx)
+        x_final = np.ascontiguousarray(x_final, dtype=np.float64).reshape(self.nx)
+        samples = int(samples)
+        if samples >= 1 and x_start.shape[0] % samples:
+            raise ValueError(f"{x_start.shape[0]} starts are no multiple of samples = {samples}")
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_track_samples(self.h, _p(x_start), _p(x_final), x_start.shape[0] // max(samples, 1), samples, float(time_step),
+                                                 int(substeps), int(max_steps), int(n_record), int(write_steps), C.byref(n)), "lqr_track_samples")
+        self.track_B = x_start.shape[0]
+        return int(n.value)
+
+    def track_download_saturation(self):
+        """n_sat [F] (plant steps on which the input was clipped), max_clip [F] (largest |u_cmd - u|) of the last flights"""
+        F = self.track_B
+        out = dict(n_sat=np.zeros(F, dtype=np.int32), max_clip=np.zeros(F))
+        _chk(self.lib.scpp_hip_lqr_track_download_saturation(self.h, _p(out["n_sat"]), _p(out["max_clip"])), "lqr_track_download_saturation")
+        return out
 
     def track_download(self):
         B = self.track_B

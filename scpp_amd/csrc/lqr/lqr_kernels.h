@@ -1,8 +1,9 @@
 // Batched LQR trajectory tracking: the two kernels behind include/scpp_hip_lqr.h.
 //   lqr_gain_kernel<Plugin>   one frozen-time LQR gain per (trajectory, node): replaces LQRTracker::LQRTracker (LQRTracker.cpp:6-28) and
 //                             ComputeLQR / careSolve / solveSchurIterative (LQR.cpp:7-109)
-//   lqr_track_kernel<Plugin>  one closed loop per trajectory on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
-//                             LQRTracker::getInput / interpolateGains (LQRTracker.cpp:43-65) and trajectoryData.hpp:41-78
+//   lqr_track_kernel<Plugin, SAT>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
+//                             LQRTracker::getInput / interpolateGains (LQRTracker.cpp:43-65) and trajectoryData.hpp:41-78; SAT: with the
+//                             plugin's input limits in the loop (the clip of LQR_sim.cpp:55-66)
 // A component of its own: it reads the model plugins' flow maps, their generated Jacobian rows and the RKF78 tableau (csrc/common.h) and nothing
 // else of the solver; the solver's sources are not touched by it.
 #pragma once
@@ -19,6 +20,36 @@ constexpr int HALF = 32;                 // lanes per Hamiltonian: lane = row, t
 constexpr int SIGN_MAX_ITERATIONS = 100; // LQR.cpp:78; the reference tests `iterations > maxIterations`, i.e. at most 101 inversions
 constexpr double SIGN_EPS = 1e-8;        // LQR.cpp:78
 constexpr int ST_OK = 0, ST_STEP_CAP = 1, ST_ITERATION_LIMIT = -1, ST_NONFINITE = -2;
+
+// ---- input limits of the tracking loop (scpp_hip_lqr_set_input_limits).  One row on the device is LIM_ROW doubles: (T_min, T_max, angle_max,
+// tan(angle_max)); the host computes the tangent once, so the device, the emulation and a host twin clip with the same number.  Every product
+// below is a statement of its own: under -ffp-contract=on nothing here is fused, and the rule rounds the same wherever it is compiled. ----
+constexpr int LIM_ROW = 4;
+// LQR_sim.cpp:55-66 in its order, on the thrust vector u[0..2]:  u_z = max(T_min, u_z);  c = tan(angle_max) u_z, |u_xy| > c: u_xy *= c / |u_xy|;
+// |u| > T_max: u *= T_max / |u|.  With T_min <= T_max cos(angle_max) (the host checks it) the result satisfies all three constraints.
+__host__ __device__ inline void saturateThrustVector(double *u, const double *lim)
+{
+    if (u[2] < lim[0])
+        u[2] = lim[0];
+    const double c = lim[3] * u[2];
+    const double xx = u[0] * u[0], yy = u[1] * u[1];
+    const double nxy = sqrt(xx + yy);
+    if (nxy > c)
+    {
+        const double s = c / nxy;
+        u[0] *= s;
+        u[1] *= s;
+    }
+    const double x2 = u[0] * u[0], y2 = u[1] * u[1], z2 = u[2] * u[2];
+    const double n = sqrt((x2 + y2) + z2);
+    if (n > lim[1])
+    {
+        const double s = lim[1] / n;
+        u[0] *= s;
+        u[1] *= s;
+        u[2] *= s;
+    }
+}
 
 // ---- LQR traits of the model plugins.  LQR_TANGENT: the Riccati equation is solved on the tangent system x = N(x) xi (NR < NX columns, orthonormal),
 // A_r = N'AN, B_r = N'B, Q_r = N'QN, K = K_r N'; the plugin supplies the rows of N. ----
@@ -49,6 +80,9 @@ struct RocketQuatLqr
                 n[7 + c] = L[row - 7][c] * s;
         }
     }
+    // u = (T_B, tau_z): the thrust vector is clipped, the roll torque passes through
+    static constexpr bool THRUST_VECTOR = true;
+    __host__ __device__ static inline void saturate(double *u, const double *lim) { saturateThrustVector(u, lim); }
 };
 struct Rocket2dLqr
 {
@@ -56,6 +90,13 @@ struct Rocket2dLqr
     static constexpr int ID = Model::MODEL_ID;
     static constexpr bool LQR_TANGENT = false;
     static constexpr int NR = Model::NX;
+    // u = (gimbal, thrust): a box (rocket2d.cpp:77-83)
+    static constexpr bool THRUST_VECTOR = false;
+    __host__ __device__ static inline void saturate(double *u, const double *lim)
+    {
+        u[0] = u[0] < -lim[2] ? -lim[2] : (u[0] > lim[2] ? lim[2] : u[0]);
+        u[1] = u[1] < lim[0] ? lim[0] : (u[1] > lim[1] ? lim[1] : u[1]);
+    }
 };
 struct Lander3dofLqr
 {
@@ -63,6 +104,9 @@ struct Lander3dofLqr
     static constexpr int ID = Model::MODEL_ID;
     static constexpr bool LQR_TANGENT = false;
     static constexpr int NR = Model::NX;
+    // u = T_I, the thrust vector in the inertial frame; angle_max is the pointing cone about (0, 0, 1)
+    static constexpr bool THRUST_VECTOR = true;
+    __host__ __device__ static inline void saturate(double *u, const double *lim) { saturateThrustVector(u, lim); }
 };
 template <class... P>
 struct LqrPluginList
@@ -411,28 +455,40 @@ __global__ void __launch_bounds__(WAVE) lqr_gain_kernel(long nodes, int K, int n
     }
 }
 
-// One closed loop per instance (one thread each: the state, the stage slopes and the gain row products live in registers).
-//   X [B][K][nx], U [B][uRows][nu] (nU rows used), T [B], par [B][np], G [B][K][nu][nx], x_start [B][nx], x_final [nx]; stop_tol > 0: also stop once
+// One closed loop per flight (one thread each: the state, the stage slopes and the gain row products live in registers).  F flights, `samples`
+// per trajectory: flight f follows trajectory f / samples (its X, U, T, G, parameter row and limits row) from its own x_start[f]; nothing is
+// replicated.
+//   X [B][K][nx], U [B][uRows][nu] (nU rows used), T [B], par [B][np], G [B][K][nu][nx], x_start [F][nx], x_final [nx]; stop_tol > 0: also stop once
 //   |x - x_final| < stop_tol (the regulator loop of LQR_sim.cpp:43-82, run on a constant two-node "trajectory")
-//   out_x [B][nx], out_u [B][nu], out_s [B][4] = (t, |x_start - x_final|, |x_end - x_final|, max |x - x_ref|), out_i [B][2] = (steps, status)
-//   record (first n_record instances, every write_steps-th step): rec_x [n_record][rec_cap][nx], rec_u [..][nu], rec_t [..], rec_n [n_record]
-template <class P>
-__global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, int uRows, const double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ T,
+//   out_x [F][nx], out_u [F][nu], out_s [F][4] = (t, |x_start - x_final|, |x_end - x_final|, max |x - x_ref|), out_i [F][2] = (steps, status)
+//   record (first n_record flights, every write_steps-th step): rec_x [n_record][rec_cap][nx], rec_u [..][nu], rec_t [..], rec_n [n_record]
+//   SAT: u = P::saturate(u_cmd) with the row lim [B or 1][LIM_ROW] of the trajectory; out_nsat [F] = plant steps with u != u_cmd, out_clip [F] =
+//   largest |u_cmd - u|.  SAT == false reads and writes none of the three (the host zeroes the two outputs) and is the loop as it was.
+template <class P, bool SAT>
+__global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int K, int nU, int uRows, const double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ T,
                                  const double *__restrict__ par, int par_stride, const double *__restrict__ G,
                                  const double *__restrict__ x_start, const double *__restrict__ x_final, double time_step, int substeps,
                                  double stop_tol, int max_steps, int n_record, int write_steps, int rec_cap, double *__restrict__ out_x,
                                  double *__restrict__ out_u, double *__restrict__ out_s, int *__restrict__ out_i, double *__restrict__ rec_x,
-                                 double *__restrict__ rec_u, double *__restrict__ rec_t, int *__restrict__ rec_n)
+                                 double *__restrict__ rec_u, double *__restrict__ rec_t, int *__restrict__ rec_n,
+                                 const double *__restrict__ lim, int lim_stride, int *__restrict__ out_nsat, double *__restrict__ out_clip)
 {
     using Model = typename P::Model;
     constexpr int NX = Model::NX, NU = Model::NU, NP = Model::NP;
     const long b = long(blockIdx.x) * blockDim.x + threadIdx.x;
     if (b >= B)
         return;
+    const long tr = b / samples; // the trajectory of this flight
     const bool foh = (nU == K);
     double p[NP], y[NX], u[NU], xf[NX], kk[RK_S][NX];
     for (int j = 0; j < NP; j++)
-        p[j] = par[b * par_stride + j];
+        p[j] = par[tr * par_stride + j];
+    double lm[SAT ? LIM_ROW : 1];
+    int n_sat = 0;
+    double max_clip = 0.;
+    if constexpr (SAT)
+        for (int j = 0; j < LIM_ROW; j++)
+            lm[j] = lim[tr * lim_stride + j];
     bool finite = true;
     double e0 = 0.;
     for (int j = 0; j < NX; j++)
@@ -444,9 +500,9 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, i
     }
     for (int j = 0; j < NU; j++)
         u[j] = 0.;
-    const double t_max = T[b];
+    const double t_max = T[tr];
     finite = finite && isFinite(t_max);
-    const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU, *Gb = G + b * K * NU * NX;
+    const double *Xb = X + tr * K * NX, *Ub = U + tr * uRows * NU, *Gb = G + tr * K * NU * NX;
     double t = 0., max_dev = 0.;
     int steps = 0, st = ST_OK, nrec = 0;
     if (!finite)
@@ -502,6 +558,25 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, i
         }
         for (int c = 0; c < NU; c++)
             u[c] = un[c];
+        if constexpr (SAT)
+        {
+            P::saturate(u, lm);
+            bool clipped = false;
+            double d2 = 0.;
+            for (int c = 0; c < NU; c++)
+            {
+                const double d = un[c] - u[c];
+                const double dd = d * d;
+                clipped = clipped || (u[c] != un[c]);
+                d2 = d2 + dd;
+            }
+            if (clipped)
+            {
+                const double clip = sqrt(d2);
+                n_sat++;
+                max_clip = clip > max_clip ? clip : max_clip;
+            }
+        }
         // scpp::simulate(model, time_step, u, u, x)   (simulation.cpp:25-42: RKF78, fixed steps; the input is constant over the step)
         double yn[NX];
         for (int j = 0; j < NX; j++)
@@ -581,6 +656,11 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int K, int nU, i
     out_i[b * 2 + 1] = st;
     if (b < n_record)
         rec_n[b] = nrec;
+    if constexpr (SAT)
+    {
+        out_nsat[b] = n_sat;
+        out_clip[b] = max_clip;
+    }
 }
 
 } // namespace lqr

@@ -63,6 +63,14 @@ struct scpp_hip_lqr_ctx
     bool have_par = false, have_traj = false, have_gains = false, gains_computed = false, have_track = false;
     int track_B = 0;
     double stop_tol = 0.;
+    // flights: xs, ox, ou, os, oi and the two saturation outputs hold fl_cap flights (batch_max at first, grown on demand by a sample fan)
+    size_t fl_cap = 0;
+    int *onsat = nullptr;
+    double *oclip = nullptr;
+    // input limits (scpp_hip_lqr_set_input_limits): rows of LIM_ROW doubles, allocated by the first call that sets some
+    double *lim = nullptr;
+    int lim_rows = 0; // 1 (shared) or the number of trajectories
+    bool have_lim = false;
 };
 
 template <class T>
@@ -171,6 +179,27 @@ static int growTo(scpp_hip_lqr_ctx *c, double **buf, size_t *cap, size_t need)
     return SCPP_OK;
 }
 
+// the per-flight buffers hold at least F flights afterwards; they only ever grow.  On failure they are gone and fl_cap == 0.
+static int growFlights(scpp_hip_lqr_ctx *c, size_t F)
+{
+    if (F <= c->fl_cap)
+        return SCPP_OK;
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    void *old[] = {c->xs, c->ox, c->ou, c->os, c->oi, c->onsat, c->oclip};
+    for (void *p : old)
+        if (p)
+            (void)hipFree(p);
+    c->xs = c->ox = c->ou = c->os = c->oclip = nullptr;
+    c->oi = c->onsat = nullptr;
+    c->fl_cap = 0;
+    c->have_track = false; // the results of the last flights went with the buffers
+    if (devAlloc(&c->xs, F * c->nx) | devAlloc(&c->ox, F * c->nx) | devAlloc(&c->ou, F * c->nu) | devAlloc(&c->os, F * 4) | devAlloc(&c->oi, F * 2) |
+        devAlloc(&c->onsat, F) | devAlloc(&c->oclip, F))
+        return SCPP_E_HIP;
+    c->fl_cap = F;
+    return SCPP_OK;
+}
+
 extern "C"
 {
 
@@ -233,6 +262,9 @@ int scpp_hip_lqr_create(scpp_hip_lqr_ctx **out, int device_id, int model_id, int
     rc |= devAlloc(&c->ou, B * nu);
     rc |= devAlloc(&c->os, B * 4);
     rc |= devAlloc(&c->oi, B * 2);
+    rc |= devAlloc(&c->onsat, B);
+    rc |= devAlloc(&c->oclip, B);
+    c->fl_cap = B;
     if (rc == 0)
     {
         HostBuf<double> one(nx > nu ? nx : nu);
@@ -259,7 +291,7 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus};
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -566,6 +598,48 @@ int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *c, double *state_std, dou
     return SCPP_OK;
 }
 
+int scpp_hip_lqr_set_input_limits(scpp_hip_lqr_ctx *c, const double *lim, int B)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!lim)
+    {
+        c->have_lim = false;
+        return SCPP_OK;
+    }
+    if (B < 1 || B > c->Bmax)
+        return SCPP_E_ARG;
+    bool thrust_vector = false;
+    (void)withLqrPlugin(c->model, [&](auto pl) {
+        thrust_vector = decltype(pl)::THRUST_VECTOR;
+        return 0;
+    });
+    HostBuf<double> rows(size_t(B) * LIM_ROW);
+    if (!rows.p)
+        return SCPP_E_HIP;
+    for (int b = 0; b < B; b++)
+    {
+        const double t_min = lim[b * 3 + 0], t_max = lim[b * 3 + 1], angle = lim[b * 3 + 2];
+        if (!allFinite(lim + b * 3, 3) || t_min < 0. || !(t_max > t_min) || !(angle > 0.) || !(angle < 1.5707963267948966))
+            return SCPP_E_ARG;
+        if (thrust_vector && t_min > t_max * std::cos(angle))
+            return SCPP_E_ARG; // the three steps end inside the set only under this condition: the T_max scaling could undo the T_min floor
+        double *r = rows.p + size_t(b) * LIM_ROW;
+        r[0] = t_min;
+        r[1] = t_max;
+        r[2] = angle;
+        r[3] = std::tan(angle);
+    }
+    DeviceGuard guard(c->device);
+    if (!c->lim && devAlloc(&c->lim, size_t(c->Bmax) * LIM_ROW))
+        return SCPP_E_HIP;
+    CHECK_HIP(hipMemcpyAsync(c->lim, rows.p, rows.n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    c->lim_rows = B;
+    c->have_lim = true;
+    return SCPP_OK;
+}
+
 int scpp_hip_lqr_set_stop_tolerance(scpp_hip_lqr_ctx *c, double stop_tol)
 {
     if (!c || !(stop_tol >= 0.) || !std::isfinite(stop_tol))
@@ -577,18 +651,28 @@ int scpp_hip_lqr_set_stop_tolerance(scpp_hip_lqr_ctx *c, double stop_tol)
 int scpp_hip_lqr_track(scpp_hip_lqr_ctx *c, const double *x_start, const double *x_final, int B, double time_step, int substeps, int max_steps,
                        int n_record, int write_steps, int *n_finite)
 {
-    if (!c || !x_start || !x_final || B < 1 || !(time_step > 0.) || !std::isfinite(time_step) || substeps < 1 || max_steps < 1 ||
-        n_record < 0 || n_record > B || (n_record > 0 && write_steps < 1))
+    return scpp_hip_lqr_track_samples(c, x_start, x_final, B, 1, time_step, substeps, max_steps, n_record, write_steps, n_finite);
+}
+
+int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *c, const double *x_start, const double *x_final, int Btraj, int samples, double time_step,
+                               int substeps, int max_steps, int n_record, int write_steps, int *n_finite)
+{
+    if (!c || !x_start || !x_final || Btraj < 1 || samples < 1 || long(Btraj) * samples > 0x7fffffffL || !(time_step > 0.) ||
+        !std::isfinite(time_step) || substeps < 1 || max_steps < 1 || n_record < 0 || n_record > long(Btraj) * samples ||
+        (n_record > 0 && write_steps < 1))
         return SCPP_E_ARG;
     if (int rc = readyToLaunch(c))
         return rc;
-    if (!c->have_gains)
-        return SCPP_E_STATE;
-    if (B != c->B)
-        return SCPP_E_ARG; // one start per trajectory
+    if (!c->have_gains || (c->have_lim && c->lim_rows != 1 && c->lim_rows != c->B))
+        return SCPP_E_STATE; // no gains, or limits for another number of trajectories
+    if (Btraj != c->B)
+        return SCPP_E_ARG; // `samples` starts per trajectory
     if (!allFinite(x_final, size_t(c->nx)))
         return SCPP_E_ARG;
+    const int B = Btraj * samples; // flights
     DeviceGuard guard(c->device);
+    if (int rc = growFlights(c, size_t(B)))
+        return rc;
     if (write_steps < 1)
         write_steps = 1;
     const int rec_cap = n_record > 0 ? (max_steps + write_steps - 1) / write_steps : 0;
@@ -611,12 +695,25 @@ int scpp_hip_lqr_track(scpp_hip_lqr_ctx *c, const double *x_start, const double 
     }
     CHECK_HIP(hipMemcpyAsync(c->xs, x_start, size_t(B) * c->nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipMemcpyAsync(c->xf, x_final, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!c->have_lim)
+    {
+        CHECK_HIP(hipMemsetAsync(c->onsat, 0, size_t(B) * sizeof(int), c->stream));
+        CHECK_HIP(hipMemsetAsync(c->oclip, 0, size_t(B) * sizeof(double), c->stream));
+    }
     const unsigned grid = unsigned((B + WAVE - 1) / WAVE);
     int rc = launchKernel(c, [&](auto pl) {
         using P = decltype(pl);
-        hipLaunchKernelGGL((lqr_track_kernel<P>), dim3(grid), dim3(WAVE), 0, c->stream, B, c->K, c->nU, c->uRows, c->tX, c->tU, c->tT,
-                           (const double *)c->par, c->par_stride, (const double *)c->G, (const double *)c->xs, (const double *)c->xf, time_step,
-                           substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn);
+        // no limits: the SAT = false instantiation, which neither reads limits nor writes the saturation outputs
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), 0, c->stream, B, samples, c->K, c->nU, c->uRows, c->tX, c->tU, c->tT,
+                               (const double *)c->par, c->par_stride, (const double *)c->G, (const double *)c->xs, (const double *)c->xf, time_step,
+                               substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
+                               (const double *)c->lim, c->lim_rows == 1 ? 0 : LIM_ROW, c->onsat, c->oclip);
+        };
+        if (c->have_lim)
+            go(lqr_track_kernel<P, true>);
+        else
+            go(lqr_track_kernel<P, false>);
     });
     if (rc)
         return rc;
@@ -677,6 +774,22 @@ int scpp_hip_lqr_track_download(scpp_hip_lqr_ctx *c, double *x, double *u, doubl
         if (status)
             status[b] = oi[b * 2 + 1];
     }
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_track_download_saturation(scpp_hip_lqr_ctx *c, int *n_sat, double *max_clip)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_track)
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t F = size_t(c->track_B);
+    if (n_sat)
+        CHECK_HIP(hipMemcpyAsync(n_sat, c->onsat, F * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (max_clip)
+        CHECK_HIP(hipMemcpyAsync(max_clip, c->oclip, F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
     return SCPP_OK;
 }
 

@@ -79,6 +79,40 @@ public:
         setInputWeights(r);
     }
 
+    // the clip of LQR_sim.cpp:55-66 for the loops simulate() flies: (T_min, T_max, angle_max in radians); off by default, and solve()
+    // stays the unlimited control law
+    void setInputLimits(const std::array<double, 3> &lim) { input_limits = lim; }
+    void setInputLimitsFromModel()
+    {
+        std::array<double, 3> lim{};
+        model->inputLimits(lim.data());
+        input_limits = lim;
+    }
+    void clearInputLimits() { input_limits.reset(); }
+
+    // LQR_sim.cpp:43-82 for every start at once, on the device: u = sat(-K (x - x_final) + u_eq) until |x - x_final| < stop_tol or sim_time,
+    // `samples` starts per regulator (they all share the one gain, so samples only shapes the fan: x_start.size() must be a multiple)
+    void simulate(const std::vector<Model::state_vector_t> &x_start, lqr_track_result_t &out, int samples = 1, double sim_time = 5., double time_step = 0.010,
+                  double stop_tol = 0.02, int n_record = 0, int write_steps = 30)
+    {
+        if (!initialized)
+            throw std::runtime_error("LQRAlgorithm::initialize() has not been called");
+        if (samples < 1 || x_start.empty() || x_start.size() % size_t(samples) != 0)
+            throw std::invalid_argument("LQRAlgorithm::simulate: the starts are no multiple of samples");
+        trajectory_data_t td;
+        td.initialize(2, true);
+        td.X[0] = td.X[1] = x_final;
+        td.U[0] = td.U[1] = u_eq;
+        td.t = sim_time;
+        const std::pair<std::array<double, NX>, std::array<double, NU>> weights{Q, R};
+        LQRTracker loop(model, std::vector<trajectory_data_t>(x_start.size() / size_t(samples), td), device, &weights);
+        loop.setGains(std::vector<LQRTracker::feedback_matrix_t>(loop.gains.size(), K));
+        loop.setStopTolerance(stop_tol);
+        if (input_limits)
+            loop.setInputLimits(std::vector<double>(input_limits->begin(), input_limits->end()));
+        loop.track(x_start, x_final, out, time_step, n_record, write_steps, 20, samples);
+    }
+
     LQRTracker::feedback_matrix_t K{};
     Model::state_vector_t x_eq{};
     Model::input_vector_t u_eq{};
@@ -91,6 +125,7 @@ private:
     bool state_weights_set = false, input_weights_set = false, initialized = false;
     Model::state_vector_t x_init{}, x_final{};
     std::optional<Model::input_vector_t> u;
+    std::optional<std::array<double, 3>> input_limits;
 };
 
 } // namespace scpp

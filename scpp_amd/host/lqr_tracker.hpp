@@ -20,6 +20,8 @@ struct lqr_track_result_t
     std::vector<Model::input_vector_t> u; // last inputs
     std::vector<double> t, initial_error, final_error, max_deviation;
     std::vector<int32_t> steps, status;
+    std::vector<int32_t> n_sat;   // plant steps on which the input limits clipped (0 without limits)
+    std::vector<double> max_clip; // largest |u_cmd - u| met (0 without limits)
     int n_finite = 0;
     // record of the first n_record flights, every write_steps-th step
     std::vector<std::vector<Model::state_vector_t>> X_sim;
@@ -198,17 +200,47 @@ public:
         }
     }
 
-    // SC_tracking.cpp:48-75 for every trajectory at once, on the device: one flight per trajectory from x_start[b]
-    void track(const std::vector<Model::state_vector_t> &x_start, const Model::state_vector_t &x_final, lqr_track_result_t &out,
-               double time_step = 0.01, int n_record = 0, int write_steps = 30, int substeps = 20)
+    // input limits inside the closed loop (scpp_hip_lqr_set_input_limits): rows (T_min, T_max, angle_max in radians), one for every trajectory
+    // or one per trajectory; empty: none (the default).  A clip, not an anti-windup design: the gains do not know about it.
+    void setInputLimits(const std::vector<double> &lim)
     {
+        if (lim.size() % 3 != 0)
+            throw std::invalid_argument("LQRTracker::setInputLimits: rows of (T_min, T_max, angle_max)");
+        check(scpp_hip_lqr_set_input_limits(ctx, lim.empty() ? nullptr : lim.data(), int(lim.size() / 3)), "scpp_hip_lqr_set_input_limits");
+    }
+    // the limits of the model's parameters: T_min, T_max, gimbal_max
+    void setInputLimitsFromModel()
+    {
+        std::vector<double> lim(3);
+        model->inputLimits(lim.data());
+        setInputLimits(lim);
+    }
+    // regulator mode (scpp_hip_lqr_set_stop_tolerance) and user-supplied gains [B][K], for LQRAlgorithm::simulate
+    void setStopTolerance(double tol) { check(scpp_hip_lqr_set_stop_tolerance(ctx, tol), "scpp_hip_lqr_set_stop_tolerance"); }
+    void setGains(const std::vector<feedback_matrix_t> &G)
+    {
+        if (G.size() != gains.size())
+            throw std::invalid_argument("LQRTracker::setGains: one gain per trajectory and node");
+        check(scpp_hip_lqr_set_gains(ctx, &G[0][0][0]), "scpp_hip_lqr_set_gains");
+        gains = G;
+    }
+
+    // SC_tracking.cpp:48-75 for every trajectory at once, on the device: `samples` flights per trajectory, flight f from x_start[f] along
+    // trajectory f / samples (samples = 1: one flight per trajectory); max_steps = 0: the longest flight time / time_step + 2
+    void track(const std::vector<Model::state_vector_t> &x_start, const Model::state_vector_t &x_final, lqr_track_result_t &out,
+               double time_step = 0.01, int n_record = 0, int write_steps = 30, int substeps = 20, int samples = 1, int max_steps = 0)
+    {
+        if (samples < 1 || x_start.size() % size_t(samples) != 0)
+            throw std::invalid_argument("LQRTracker::track: the starts are no multiple of samples");
         const int B = int(x_start.size());
         double t_max = 0.;
         for (const auto &td : tds)
             t_max = std::max(t_max, td.t);
-        const int max_steps = int(std::ceil(t_max / time_step)) + 2;
-        check(scpp_hip_lqr_track(ctx, &x_start[0][0], x_final.data(), B, time_step, substeps, max_steps, n_record, write_steps, &out.n_finite),
-              "scpp_hip_lqr_track");
+        if (max_steps < 1)
+            max_steps = int(std::ceil(t_max / time_step)) + 2;
+        check(scpp_hip_lqr_track_samples(ctx, &x_start[0][0], x_final.data(), B / samples, samples, time_step, substeps, max_steps, n_record, write_steps,
+                                         &out.n_finite),
+              "scpp_hip_lqr_track_samples");
         const size_t nB = size_t(B);
         out.x.resize(nB);
         out.u.resize(nB);
@@ -219,6 +251,9 @@ public:
         check(scpp_hip_lqr_track_download(ctx, &out.x[0][0], &out.u[0][0], out.t.data(), out.steps.data(), out.status.data(),
                                           out.initial_error.data(), out.final_error.data(), out.max_deviation.data()),
               "scpp_hip_lqr_track_download");
+        out.n_sat.assign(nB, 0);
+        out.max_clip.assign(nB, 0.);
+        check(scpp_hip_lqr_track_download_saturation(ctx, out.n_sat.data(), out.max_clip.data()), "scpp_hip_lqr_track_download_saturation");
         out.X_sim.clear();
         out.U_sim.clear();
         out.t_sim.clear();

@@ -87,6 +87,13 @@ public:
             x[size_t(j)] *= r_scale;
         u[1] *= m_scale * r_scale;
     }
+    // (T_min, T_max, gimbal_max in radians): the limits row of scpp_hip_lqr_set_input_limits
+    void inputLimits(double *lim) const
+    {
+        lim[0] = p.T_min;
+        lim[1] = p.T_max;
+        lim[2] = p.gimbal_max;
+    }
     void flowParams(double *par) const
     {
         param_vector_t q;

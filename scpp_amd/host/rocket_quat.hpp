@@ -169,6 +169,14 @@ public:
         u[3] *= m_scale * r_scale * r_scale;
     }
 
+    // (T_min, T_max, gimbal_max in radians): the limits row of scpp_hip_lqr_set_input_limits
+    void inputLimits(double *lim) const
+    {
+        lim[0] = p.abi.T_min;
+        lim[1] = p.abi.T_max;
+        lim[2] = p.abi.gimbal_max;
+    }
+
     // flow-map parameters in SI units for the plant simulation (rocketQuat.cpp:168-173 without scaling)
     void flowParams(double *par) const
     {

@@ -9,6 +9,13 @@
 //                         S(0) = diag(initial_std)^2 and W = diag(disturbance_std)^2 from the optional vectors initial_std / disturbance_std of
 //                         LQR.info (absent: 0); --covariance-steps n RKF78 steps per segment (5).  Writes state_std.txt (one node per row) and
 //                         input_cov.txt (one node per row, the nu x nu matrix row-major) of instance 0 next to X.txt
+//   --saturate          : input limits inside the closed loop (scpp_hip_lqr_set_input_limits), from the model's parameters T_min, T_max,
+//                         gimbal_max.  Writes n_sat.txt (plant steps on which the input was clipped) and max_clip.txt (largest |u_cmd - u|),
+//                         one flight per row, next to X.txt
+//                         (--saturate and --samples also write x_end.txt: the final state of every flight, one per row)
+//   --samples N         : N flights per trajectory (scpp_hip_lqr_track_samples): flight 0 of trajectory b from the initial state the trajectory
+//                         was solved for, flights 1 .. N-1 from states drawn by the same randomisation (instances batch + b (N - 1) + s - 1 of
+//                         --seed); the trajectories and gains are neither copied nor recomputed
 // Writes <out>/output/<Model>/SC_tracking/<time>/0/{X,U,t}.txt of instance 0 (every 30th step, like write_steps of the reference) and prints
 // gains/s, tracked plant steps/s and the distribution of the final error.
 #include <algorithm>
@@ -32,8 +39,8 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
-    bool covariance = false;
-    int covariance_steps = 5;
+    bool covariance = false, saturate = false;
+    int covariance_steps = 5, samples = 1;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
     for (int i = 1; i < argc; i++)
@@ -76,6 +83,17 @@ int main(int argc, char **argv)
             covariance = true;
         else if (!std::strcmp(argv[i], "--covariance-steps"))
             covariance_steps = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--saturate"))
+            saturate = true;
+        else if (!std::strcmp(argv[i], "--samples"))
+        {
+            samples = std::atoi(next());
+            if (samples < 1)
+            {
+                std::fprintf(stderr, "--samples %d: at least 1\n", samples);
+                return 2;
+            }
+        }
         else
         {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -145,14 +163,28 @@ int main(int argc, char **argv)
                         rhs, 1e3 * t_cov, cov.n_ok, N);
         }
 
+        // the starts: `samples` per trajectory, the first of each the state its trajectory was solved for
+        std::vector<Model::state_vector_t> x_starts;
+        for (size_t b = 0; b < N; b++)
+            for (int s = 0; s < samples; s++)
+            {
+                Model inst = *model;
+                if (s > 0)
+                    inst.p.randomizeInitialState(seed, uint64_t(batch > 0 ? batch : 0) + uint64_t(b) * uint64_t(samples - 1) + uint64_t(s - 1));
+                x_starts.push_back(s > 0 ? inst.p.x_init : x_inits[b]);
+            }
+        const size_t F = x_starts.size();
+        if (saturate)
+            tracker.setInputLimitsFromModel();
+
         // start simulation
         scpp::lqr_track_result_t sim;
         t0 = seconds();
-        tracker.track(x_inits, model->p.x_final, sim, time_step, 1, 30);
+        tracker.track(x_starts, model->p.x_final, sim, time_step, 1, 30, 20, samples);
         const double t_run = seconds() - t0;
         long steps = 0;
         std::vector<double> rel;
-        for (size_t b = 0; b < N; b++)
+        for (size_t b = 0; b < F; b++)
         {
             steps += sim.steps[b];
             if (sim.status[b] != SCPP_LQR_NONFINITE && sim.initial_error[b] > 0.)
@@ -160,7 +192,20 @@ int main(int argc, char **argv)
         }
         std::sort(rel.begin(), rel.end());
         std::printf("Simulating %zu trajectories.\nFinished after %d steps (instance 0), %ld plant steps in %.2f ms: %.0f steps/s; %d of %zu flights finite\n", N,
-                    sim.steps[0] + 1, steps, 1e3 * t_run, double(steps) / t_run, sim.n_finite, N);
+                    sim.steps[0] + 1, steps, 1e3 * t_run, double(steps) / t_run, sim.n_finite, F);
+        if (samples > 1)
+            std::printf("Sample fan: %d flights per trajectory, %zu flights\n", samples, F);
+        if (saturate)
+        {
+            size_t clipped = 0;
+            double worst = 0.;
+            for (size_t f = 0; f < F; f++)
+            {
+                clipped += sim.n_sat[f] > 0;
+                worst = std::max(worst, sim.max_clip[f]);
+            }
+            std::printf("Input limits: %zu of %zu flights clipped on at least one step, largest clip %.6g\n", clipped, F, worst);
+        }
         if (!rel.empty())
             std::printf("Final error: %.4f%% (instance 0); over the batch min %.4f%% median %.4f%% max %.4f%%\n",
                         100. * sim.final_error[0] / sim.initial_error[0], rel.front(), rel[rel.size() / 2], rel.back());
@@ -174,6 +219,25 @@ int main(int argc, char **argv)
             std::ofstream f(outputPath / "t.txt");
             for (double t : sim.t_sim.at(0))
                 f << t << "\n";
+        }
+        if (saturate || samples > 1)
+        {
+            // the final state of every flight, one per row, round-trip precision
+            std::ofstream fx(outputPath / "x_end.txt");
+            fx.precision(17);
+            for (size_t f = 0; f < F; f++)
+                for (size_t j = 0; j < sim.x[f].size(); j++)
+                    fx << sim.x[f][j] << (j + 1 < sim.x[f].size() ? ", " : "\n");
+        }
+        if (saturate)
+        {
+            std::ofstream fn(outputPath / "n_sat.txt"), fc(outputPath / "max_clip.txt");
+            fc.precision(17);
+            for (size_t f = 0; f < F; f++)
+            {
+                fn << sim.n_sat[f] << "\n";
+                fc << sim.max_clip[f] << "\n";
+            }
         }
         if (covariance)
         {

@@ -2,7 +2,7 @@
 
     LQRTracker     scpp_core/include/LQRTracker.hpp, src/LQRTracker.cpp:6-65 and the closed loop of scpp/src/SC_tracking.cpp:48-75
     LQRAlgorithm   scpp_core/src/LQRAlgorithm.cpp:6-75 (one gain at the model's operating point)
-    LQRSim         scpp/src/LQR_sim.cpp:20-82 (without its input clipping, which does not compile for a two-input model)
+    LQRSim         scpp/src/LQR_sim.cpp:20-82 (its input clipping, LQR_sim.cpp:55-66, is setInputLimits: off by default)
 
 Every call handles B trajectories / closed loops.  The gains and the flights are computed by the HIP kernels of libscpp_lqr.so; only
 getInput (a spot check of one input) is host arithmetic.  There is no CPU fallback."""
@@ -53,6 +53,14 @@ def si_flow_params(model):
         return np.asarray(model.flow_params(nondimensionalize=False), dtype=np.float64)
     except TypeError:  # Rocket2D has SI parameters only
         return np.asarray(model.flow_params(), dtype=np.float64)
+
+
+def model_input_limits(model):
+    """the limits row (T_min, T_max, angle_max in radians) of scpp_hip_lqr_set_input_limits from a model's parameters: T_min, T_max and
+    gimbal_max (RocketQuat, Rocket2D) or pointing_max (Lander3dof), in SI units as the parameter files give them"""
+    p = model.p
+    angle = p.gimbal_max if hasattr(p, "gimbal_max") else p.pointing_max
+    return np.array([p.T_min, p.T_max, angle], dtype=np.float64)
 
 
 class LQRTracker:
@@ -157,15 +165,31 @@ class LQRTracker:
         x_ref = X[i] + a * (X[i + 1] - X[i])
         return -(G[i] + a * (G[j] - G[i])) @ (np.asarray(x, dtype=np.float64) - x_ref) + U[i] + a * (U[j] - U[i])
 
-    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30):
-        """The loop of SC_tracking.cpp:48-75 from x_start [B][nx], one flight per trajectory, on the device.  Returns x, u, t, steps, status,
-        err0, err1 (|x - x_final| at start / end), max_dev (largest |x - x_ref|), n_finite and, with n_record > 0, `record`."""
+    def setInputLimits(self, lim=None):
+        """Input limits inside the closed loop: None (the default) none, "model" the row of the model's parameters (model_input_limits), or
+        an array (T_min, T_max, angle_max in radians), one row for all trajectories or [B][3].  The loop then applies u = sat(u_cmd)
+        (include/scpp_hip_lqr.h has the rule).  A clip, not an anti-windup design: the gains and the covariance sweep do not know about it."""
+        if isinstance(lim, str):
+            if lim != "model":
+                raise ValueError(f"lim = {lim!r}: None, 'model' or an array")
+            lim = model_input_limits(self.model)
+        self.ctx.set_input_limits(lim)
+
+    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30, samples=1):
+        """The loop of SC_tracking.cpp:48-75 on the device, `samples` flights per trajectory from x_start [B * samples][nx] (flight f follows
+        trajectory f // samples; samples = 1: one flight per trajectory).  Returns x, u, t, steps, status, err0, err1 (|x - x_final| at
+        start / end), max_dev (largest |x - x_ref|), n_sat (plant steps on which the input limits clipped), max_clip (largest
+        |u_cmd - u|; both 0 without limits), n_finite and, with n_record > 0, `record` (of the first n_record flights)."""
         x_final = self.model.p.x_final if x_final is None else x_final
         x_final = np.array(list(x_final), dtype=np.float64)
         if max_steps is None:
             max_steps = int(math.ceil(float(np.nanmax(self.t)) / time_step)) + 2
-        n_finite = self.ctx.track(x_start, x_final, time_step, substeps, max_steps, n_record, write_steps)
+        if samples == 1:
+            n_finite = self.ctx.track(x_start, x_final, time_step, substeps, max_steps, n_record, write_steps)
+        else:
+            n_finite = self.ctx.track_samples(x_start, x_final, samples, time_step, substeps, max_steps, n_record, write_steps)
         out = self.ctx.track_download()
+        out.update(self.ctx.track_download_saturation())
         out["n_finite"] = n_finite
         if n_record > 0:
             out["record"] = self.ctx.track_record()
@@ -195,6 +219,7 @@ class LQRAlgorithm:
         self.model, self.batch_max, self.device, self.library = model, batch_max, device, library
         self.initialized = False
         self.x_init = self.x_final = self.u = None
+        self.input_limits = None
         self.loadParameters()
 
     def loadParameters(self):
@@ -207,6 +232,11 @@ class LQRAlgorithm:
 
     def setInputWeights(self, w):
         self.R = np.asarray(w, dtype=np.float64)
+
+    def setInputLimits(self, lim=None):
+        """the clip of LQR_sim.cpp:55-66 for the loops LQRSim flies with this algorithm: None (the default) none, "model" the limits of the
+        model's parameters, or a row (T_min, T_max, angle_max in radians); solve() stays the unlimited control law"""
+        self.input_limits = lim
 
     def initialize(self):
         """LQRAlgorithm.cpp:11-25: the gain kernel on a two-node constant 'trajectory' at the operating point"""
@@ -243,6 +273,11 @@ class LQRSim:
 
     def __init__(self, algorithm, sim_time=5.0, time_step=0.010, stop_tol=0.02):
         self.alg, self.sim_time, self.time_step, self.stop_tol = algorithm, sim_time, time_step, stop_tol
+        self.input_limits = algorithm.input_limits
+
+    def setInputLimits(self, lim=None):
+        """as LQRTracker.setInputLimits, for the loops of run(); starts as the algorithm's setting"""
+        self.input_limits = lim
 
     def run(self, x_start, x_final=None, n_record=0, write_steps=30, substeps=20):
         a = self.alg
@@ -254,6 +289,7 @@ class LQRSim:
                          device=a.device, library=a.library, compute=False)
         trk.setGains(np.tile(a.K, (B, 2, 1, 1)))
         trk.ctx.set_stop_tolerance(self.stop_tol)
+        trk.setInputLimits(self.input_limits)
         out = trk.track(x_start, x_final, self.time_step, substeps, None, n_record, write_steps)
         trk.close()
         return out

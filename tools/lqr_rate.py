@@ -1,7 +1,7 @@
 """LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
-    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--out FILE]
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
 segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
@@ -10,6 +10,18 @@ segment), the same N flights under those gains.  It only ADDS keys (riccati_*); 
 the gains the tracker holds at that point: the Riccati gains when --riccati is given too, else the frozen-time ones.  It only ADDS keys
 (covariance_*).  The initial covariance is diagonal: 1 % of the largest |state| over the batch (a floor of 1e-3) as the standard deviation of
 every state; the disturbance intensity is 1 % of that variance per second.
+
+--saturate (measure(saturate=True)) flies the N flights of the default leg again, from the same starts and under the same frozen-time gains,
+with the input limits of the model's parameters inside the loop (LQRTracker.setInputLimits("model")), and once more without them timed the
+same way.  It only ADDS keys (saturate_*): the time of the flight call with and without limits and their ratio, plant steps/s, the share
+of flights with n_sat > 0, and the final errors with and without limits on the same starts.
+
+--samples N[,N..] (measure(samples=[..])) flies, for each N, N flights per trajectory as one fan (scpp_hip_lqr_track_samples) under the
+frozen-time gains, without limits unless --saturate is given too: flight 0 of a trajectory starts where the trajectory was solved from, the
+others 1 % (Gaussian, fixed seed) off that state.  It only ADDS the key samples_legs, one entry per N.
+
+The flight call of these two legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
+best of --repeat.
 """
 import argparse
 import json
@@ -24,7 +36,7 @@ import numpy as np  # noqa: E402
 import scpp_amd  # noqa: E402
 
 
-def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None):
+def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=()):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -49,6 +61,9 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
         t = time.perf_counter()
         out = trk.track(x0)
         tt.append(time.perf_counter() - t)
+    sat = saturate_leg(trk, x0, repeat) if saturate else {}
+    if samples:
+        sat["samples_legs"] = [samples_leg(trk, x0, int(N), repeat, bool(saturate)) for N in samples]
     ric = riccati_leg(trk, x0, int(riccati), repeat) if riccati else {}
     if covariance:
         ric.update(covariance_leg(trk, int(covariance), repeat, "riccati" if riccati else "frozen"))
@@ -71,8 +86,66 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
         "max_excursion_p50": float(np.median(out["max_dev"][fin])) if fin.any() else None,
         "timing": f"wall clock, best of {repeat}; gains include the download of the per-node status, flights the upload of the starts and the download of the results",
     }
+    res.update(sat)
     res.update(ric)
     return res
+
+
+def time_flights(trk, xs, samples, repeat):
+    """best-of-repeat wall time of the flight call alone (upload of the starts, kernel, synchronisation), then the downloaded results"""
+    x_final = np.array(list(trk.model.p.x_final), dtype=np.float64)
+    max_steps = int(np.ceil(float(np.nanmax(trk.t)) / 0.01)) + 2
+    tt = []
+    for _ in range(repeat + 1):  # the first call is the warm-up (code object of this instantiation, growth of the flight buffers)
+        t = time.perf_counter()
+        trk.ctx.track_samples(xs, x_final, samples, 0.01, 20, max_steps)
+        tt.append(time.perf_counter() - t)
+    out = trk.ctx.track_download()
+    out.update(trk.ctx.track_download_saturation())
+    return min(tt[1:]), out
+
+
+def final_errors(out):
+    e = out["err1"][out["status"] != -2]
+    return [float(v) for v in np.percentile(e, [5, 50, 95])] if e.size else []
+
+
+def saturate_leg(trk, x0, repeat):
+    """the default leg's flights with the model's input limits in the loop, and without them, timed the same way on the same starts"""
+    trk.setInputLimits(None)
+    t_off, off = time_flights(trk, x0, 1, repeat)
+    trk.setInputLimits("model")
+    t_on, on = time_flights(trk, x0, 1, repeat)
+    trk.setInputLimits(None)
+    steps = int(on["steps"].sum())
+    return {
+        "saturate_limits": [float(v) for v in scpp_amd.model_input_limits(trk.model)],
+        "saturate_flight_call_s": t_on, "saturate_off_flight_call_s": t_off, "saturate_over_off": t_on / t_off,
+        "saturate_plant_steps": steps, "saturate_plant_steps_per_s": steps / t_on,
+        "saturate_off_plant_steps": int(off["steps"].sum()), "saturate_off_plant_steps_per_s": float(off["steps"].sum() / t_off),
+        "saturate_flights_clipped_share": float((on["n_sat"] > 0).mean()), "saturate_steps_clipped_share": float(on["n_sat"].sum() / max(steps, 1)),
+        "saturate_max_clip_p50_max": [float(np.median(on["max_clip"])), float(on["max_clip"].max())],
+        "saturate_flights_completed": int((on["status"] == 0).sum()), "saturate_flights_nonfinite": int((on["status"] == -2).sum()),
+        "saturate_final_error_p5_p50_p95": final_errors(on), "saturate_off_final_error_p5_p50_p95": final_errors(off),
+        "saturate_off_n_sat_total": int(off["n_sat"].sum()),
+    }
+
+
+def samples_leg(trk, x0, N, repeat, saturate):
+    """N flights per trajectory as one fan: flight 0 from the trajectory's own start, the others 1 % off it"""
+    xs = np.repeat(x0, N, axis=0).reshape(x0.shape[0], N, -1)
+    xs[:, 1:] *= 1.0 + 0.01 * np.random.default_rng(20261018).standard_normal(xs[:, 1:].shape)
+    xs = xs.reshape(-1, x0.shape[1])
+    trk.setInputLimits("model" if saturate else None)
+    t, out = time_flights(trk, xs, N, repeat)
+    trk.setInputLimits(None)
+    steps = int(out["steps"].sum())
+    return {
+        "samples": N, "flights": int(xs.shape[0]), "limits": bool(saturate), "flight_call_s": t, "plant_steps": steps, "plant_steps_per_s": steps / t,
+        "wavefronts": int((xs.shape[0] + 63) // 64), "flights_completed": int((out["status"] == 0).sum()),
+        "flights_nonfinite": int((out["status"] == -2).sum()), "flights_clipped_share": float((out["n_sat"] > 0).mean()),
+        "final_error_p5_p50_p95": final_errors(out),
+    }
 
 
 def riccati_leg(trk, x0, steps, repeat):
@@ -139,9 +212,12 @@ if __name__ == "__main__":
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--riccati", type=int, default=0, help="RKF78 steps per segment of the finite-horizon leg (0: no such leg)")
     ap.add_argument("--covariance", type=int, default=0, help="RKF78 steps per segment of the covariance leg (0: no such leg)")
+    ap.add_argument("--saturate", action="store_true", help="the flights again with the model's input limits in the loop")
+    ap.add_argument("--samples", default="", help="comma-separated flights per trajectory of the sample-fan legs, e.g. 1,4,16")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance)
+    res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
+                  samples=[int(v) for v in a.samples.split(",") if v])
     line = json.dumps(res)
     print(line)
     if a.out:
