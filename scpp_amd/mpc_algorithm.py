@@ -38,8 +38,8 @@ class MPCAlgorithm:
     def setInputWeights(self, intermediate):
         self.input_weights = np.asarray(intermediate, dtype=np.float64)
 
-    def initialize(self, feastol=1e-8, abstol=1e-8, reltol=1e-8, maxit=50):
-        """MPCAlgorithm.cpp:34-69: linearise at the operating point, discretise exactly, build the problem (once)."""
+    def options(self, feastol=1e-8, abstol=1e-8, reltol=1e-8, maxit=50):
+        """the scpp_mpc_opts block of this configuration (what initialize() hands to scpp_hip_mpc_setup)"""
         p = self.model.p
         if p.constrain_initial_final:
             raise RuntimeError("constrain_initial_final must be disabled for MPC (config/Rocket2D/model.info: "
@@ -60,6 +60,11 @@ class MPCAlgorithm:
         o.gimbal_max, o.T_min, o.T_max = p.gimbal_max, p.T_min, p.T_max
         o.x_scale_ref = math.hypot(p.x_init[0], p.x_init[1])
         o.feastol, o.abstol, o.reltol, o.maxit = feastol, abstol, reltol, maxit
+        return o
+
+    def initialize(self, feastol=1e-8, abstol=1e-8, reltol=1e-8, maxit=50):
+        """MPCAlgorithm.cpp:34-69: linearise at the operating point, discretise exactly, build the problem (once)."""
+        o = self.options(feastol, abstol, reltol, maxit)
         self.ctx = Context(MODEL_ROCKET2D, K=max(self.K, 3), batch_max=self.batch_max, device=self.device, library=self.library)
         self.ctx.mpc_setup(o, self.model.flow_params())
         self.A, self.B, self.z = self.ctx.mpc_model()
