@@ -19,6 +19,8 @@
  *       (the differential Riccati equation along the trajectory)               scpp_hip_lqr_compute_gains_riccati, _download_riccati
  *   nothing: the reference has no covariance analysis                                         scpp_hip_lqr_set_covariance_inputs,
  *       (the closed-loop Lyapunov equation along the trajectory)               scpp_hip_lqr_propagate_covariance, _download_covariance
+ *   nothing: the reference has no sampled-data controller                                     scpp_hip_lqr_compute_gains_discrete, _download_discrete,
+ *       (the discrete Riccati recursion over the segments' transition matrices) scpp_hip_lqr_set_feedback_hold
  *
  * Deviations, all deliberate:
  *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
@@ -46,6 +48,21 @@
  *     segment; stage s of step n sits at a = (n + c_s) / steps.  Node k records S(t_k) and the input covariance G[k] S(t_k) G[k]' with the
  *     node's own gain; node 0 records S0 exactly.  S is kept symmetric BY CONSTRUCTION (A_cl S and S A_cl' are both formed, from the same
  *     products in the same order); it is never symmetrised, which is why S0 has to be symmetric to the bit.
+ *   - scpp_hip_lqr_compute_gains_discrete is an addition too: the gains of a loop that updates its correction only at the nodes and holds it
+ *     over a segment (scpp_hip_lqr_set_feedback_hold flies such a loop).  For one trajectory of K nodes and flight time T, dt = T / (K - 1).
+ *     Inside segment i at fraction a in [0, 1] the reference is x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]), j = i+1 (first-order
+ *     hold) or i (zero-order hold); the segment index is the loop's and is never recomputed from the time.  A correction du_i is added to the
+ *     reference input and held constant over segment i, under either hold of the reference.  The deviation then obeys
+ *     dx_{i+1} = Phi_i dx_i + Gamma_i du_i with d[Phi | Gamma]/dt = A(t) [Phi | Gamma] + [0 | B(t)], [Phi | Gamma](t_i) = [I | 0]; A, B are the
+ *     generated Jacobian rows at (x, u) on the full state of every model (RocketQuat: 14 states, no tangent system).  The equation is integrated
+ *     forwards over the segment with steps >= 1 fixed RKF78 steps (the plant step's tableau and 8th-order weights); stage s of step n sits at
+ *     a = (n + c_s) / steps.  The recursion runs backwards, i = K-2 .. 0, from P_{K-1} = Qf, with the stage weights Q dt and R dt (one LQR.info
+ *     means the same under this law and under the Riccati-ODE law, which the recursion tends to as dt -> 0):
+ *         S_i = R dt + Gamma_i'P_{i+1} Gamma_i,   N_i = Gamma_i'P_{i+1} Phi_i,   L_i L_i' = S_i (Cholesky, lower),   Y_i = L_i^-1 N_i,
+ *         K_i = L_i^-T Y_i,                       P_i = Q dt + Phi_i'P_{i+1} Phi_i - Y_i'Y_i.
+ *     Node K-1 has no segment behind it: its gain is a copy of K_{K-2} and its P is Qf.  P is symmetric TO THE BIT at every node: Y'Y is by
+ *     construction, and Phi'(P Phi) is symmetrised once per node, (F + F') / 2.  The covariance sweep does NOT know this law's hold: it describes
+ *     the continuous loop u = u_ref - K_t (x - x_ref), whatever gains it is given.
  *
  *   - input limits (scpp_hip_lqr_set_input_limits) are an addition to the tracking loop, off by default: with limits (T_min, T_max, angle_max)
  *     the loop applies u = sat(u_cmd), u_cmd = -K_t (x - x_ref) + u_ref computed as without them.  A non-finite u_cmd retires the flight with
@@ -119,6 +136,25 @@ extern "C"
     int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *ctx, int steps, int keep_p, int *n_ok);
     /* P [B][K][nx][nx] of the last sweep (zeros on failed nodes); SCPP_E_STATE unless the last gain computation was a sweep with keep_p != 0 */
     int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *ctx, double *P);
+    /* sampled-data gains (the definition is above): one discrete Riccati recursion per trajectory from P_{K-1} = Qf
+       (scpp_hip_lqr_set_terminal_weights; default Q), steps >= 1 RKF78 steps per segment for [Phi | Gamma] (SCPP_E_ARG otherwise).  Gains,
+       status and the count land where scpp_hip_lqr_download_gains reads them (the count: RKF78 steps behind the node, (K-1-k) steps); node
+       K-1 carries a copy of node K-2's gain.  A trajectory with a non-finite node, input or flight time gets SCPP_LQR_NONFINITE and zero gains
+       on every node; a P, Phi, Gamma or pivot of S that turns non-finite or non-positive in segment k does the same for node k and every
+       earlier node (segment K-2 takes node K-1 with it, whose gain it defines).  Nothing non-finite is ever written.  keep != 0 also keeps
+       P of every node and Phi, Gamma of every segment for scpp_hip_lqr_download_discrete (the buffers are allocated on the first such
+       request).  *n_ok (optional) = nodes with status 0.  SCPP_E_STATE as scpp_hip_lqr_compute_gains. */
+    int scpp_hip_lqr_compute_gains_discrete(scpp_hip_lqr_ctx *ctx, int steps, int keep, int *n_ok);
+    /* P [B][K][nx][nx], Phi [B][K-1][nx][nx], Gamma [B][K-1][nx][nu] of the last discrete sweep (zeros on failed nodes and their segments); any
+       pointer may be NULL.  SCPP_E_STATE unless the last gain computation was scpp_hip_lqr_compute_gains_discrete with keep != 0. */
+    int scpp_hip_lqr_download_discrete(scpp_hip_lqr_ctx *ctx, double *P, double *Phi, double *Gamma);
+    /* when the tracking loop updates its feedback term.  mode 0 (the default): on every plant step, u_cmd = u_ref(t) - K_t (x - x_ref(t)).
+       mode 1: held over a segment: du = -G[i] (x - x_ref(t)) is latched at the first plant step whose segment index i differs from the
+       latched one (flight start counts as such a step), and u_cmd = u_ref(t) + du on every plant step, u_ref interpolated as in mode 0.
+       max_dev, the non-finite retirement, input limits (the clip acts on u_cmd), the record, sample fans and the stop tolerance work as in
+       mode 0.  Anything else: SCPP_E_ARG.  The mode stays until it is set again; it invalidates neither gains nor a covariance sweep (which
+       describes the continuous loop of mode 0). */
+    int scpp_hip_lqr_set_feedback_hold(scpp_hip_lqr_ctx *ctx, int mode);
     /* gains [B][K][nu][nx], status [B][K] int32, iters [B][K] int32 (sign iterations, or RKF78 steps behind the node); any pointer may be NULL */
     int scpp_hip_lqr_download_gains(scpp_hip_lqr_ctx *ctx, double *gains, int *status, int *iters);
     /* user-supplied gains [B][K][nu][nx] for the trajectories set before; non-finite entries are refused (SCPP_E_ARG) */

@@ -485,6 +485,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_set_terminal_weights", "scpp_hip_lqr_compute_gains_riccati", "scpp_hip_lqr_download_riccati",
     "scpp_hip_lqr_set_covariance_inputs", "scpp_hip_lqr_propagate_covariance", "scpp_hip_lqr_download_covariance",
     "scpp_hip_lqr_set_input_limits", "scpp_hip_lqr_track_samples", "scpp_hip_lqr_track_download_saturation",
+    "scpp_hip_lqr_compute_gains_discrete", "scpp_hip_lqr_download_discrete", "scpp_hip_lqr_set_feedback_hold",
 ]
 _lqr_libs = {}
 
@@ -584,6 +585,23 @@ class LqrContext:
         P = np.zeros((self.B, self.K, self.nx, self.nx))
         _chk(self.lib.scpp_hip_lqr_download_riccati(self.h, _p(P)), "lqr_download_riccati")
         return P
+
+    def compute_gains_discrete(self, steps=5, keep=False):
+        """sampled-data gains (one discrete Riccati recursion per trajectory); returns the number of nodes with status 0"""
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_compute_gains_discrete(self.h, int(steps), int(bool(keep)), C.byref(n)), "lqr_compute_gains_discrete")
+        return int(n.value)
+
+    def download_discrete(self):
+        """P [B][K][nx][nx], Phi [B][K-1][nx][nx], Gamma [B][K-1][nx][nu] of the last discrete sweep (keep=True)"""
+        out = dict(P=np.zeros((self.B, self.K, self.nx, self.nx)), Phi=np.zeros((self.B, self.K - 1, self.nx, self.nx)),
+                   Gamma=np.zeros((self.B, self.K - 1, self.nx, self.nu)))
+        _chk(self.lib.scpp_hip_lqr_download_discrete(self.h, _p(out["P"]), _p(out["Phi"]), _p(out["Gamma"])), "lqr_download_discrete")
+        return out
+
+    def set_feedback_hold(self, mode):
+        """0: the feedback term changes on every plant step (the default); 1: it is latched at each node and held over the segment"""
+        _chk(self.lib.scpp_hip_lqr_set_feedback_hold(self.h, int(mode)), "lqr_set_feedback_hold")
 
     def set_covariance_inputs(self, sigma0, w=None):
         """sigma0 [B][nx][nx] or one [nx][nx] for every trajectory (symmetric to the bit), w [nx] >= 0 the diagonal of the disturbance

@@ -1,7 +1,7 @@
 // Batched LQR trajectory tracking: the two kernels behind include/scpp_hip_lqr.h.
 //   lqr_gain_kernel<Plugin>   one frozen-time LQR gain per (trajectory, node): replaces LQRTracker::LQRTracker (LQRTracker.cpp:6-28) and
 //                             ComputeLQR / careSolve / solveSchurIterative (LQR.cpp:7-109)
-//   lqr_track_kernel<Plugin, SAT>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
+//   lqr_track_kernel<Plugin, SAT, HOLD>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
 //                             LQRTracker::getInput / interpolateGains (LQRTracker.cpp:43-65) and trajectoryData.hpp:41-78; SAT: with the
 //                             plugin's input limits in the loop (the clip of LQR_sim.cpp:55-66)
 // A component of its own: it reads the model plugins' flow maps, their generated Jacobian rows and the RKF78 tableau (csrc/common.h) and nothing
@@ -464,7 +464,10 @@ __global__ void __launch_bounds__(WAVE) lqr_gain_kernel(long nodes, int K, int n
 //   record (first n_record flights, every write_steps-th step): rec_x [n_record][rec_cap][nx], rec_u [..][nu], rec_t [..], rec_n [n_record]
 //   SAT: u = P::saturate(u_cmd) with the row lim [B or 1][LIM_ROW] of the trajectory; out_nsat [F] = plant steps with u != u_cmd, out_clip [F] =
 //   largest |u_cmd - u|.  SAT == false reads and writes none of the three (the host zeroes the two outputs) and is the loop as it was.
-template <class P, bool SAT>
+//   HOLD: the feedback term is held over a segment (scpp_hip_lqr_set_feedback_hold): du = -G[i] (x - x_ref(t)) is latched at the first plant step
+//   whose segment index i differs from the latched one (flight start included) and u_cmd = u_ref(t) + du on every plant step; everything else as
+//   without it.  HOLD == false is the loop as it was.
+template <class P, bool SAT, bool HOLD = false>
 __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int K, int nU, int uRows, const double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ T,
                                  const double *__restrict__ par, int par_stride, const double *__restrict__ G,
                                  const double *__restrict__ x_start, const double *__restrict__ x_final, double time_step, int substeps,
@@ -505,6 +508,8 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int
     const double *Xb = X + tr * K * NX, *Ub = U + tr * uRows * NU, *Gb = G + tr * K * NU * NX;
     double t = 0., max_dev = 0.;
     int steps = 0, st = ST_OK, nrec = 0;
+    double du[HOLD ? NU : 1];
+    long latched = -1; // HOLD: the segment du was latched in
     if (!finite)
     {
         st = ST_NONFINITE; // retires at once (the reference throws "State has NaN", SC_tracking.cpp:71-74): zeros, no non-finite output
@@ -537,16 +542,38 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int
         }
         dev = sqrt(dev);
         max_dev = dev > max_dev ? dev : max_dev;
-        for (int c = 0; c < NU; c++)
+        if constexpr (HOLD)
         {
-            const double u0 = Ub[i * NU + c], u1 = Ub[iu1 * NU + c];
-            double acc = 0.;
-            for (int j = 0; j < NX; j++)
+            if (i != latched)
             {
-                const double g0 = Gb[(i * NU + c) * NX + j], g1 = Gb[(iu1 * NU + c) * NX + j];
-                acc += (g0 + a * (g1 - g0)) * dx[j];
+                for (int c = 0; c < NU; c++)
+                {
+                    double acc = 0.;
+                    for (int j = 0; j < NX; j++)
+                        acc += Gb[(i * NU + c) * NX + j] * dx[j];
+                    du[c] = -acc;
+                }
+                latched = i;
             }
-            un[c] = -acc + (u0 + a * (u1 - u0));
+            for (int c = 0; c < NU; c++)
+            {
+                const double u0 = Ub[i * NU + c], u1 = Ub[iu1 * NU + c];
+                un[c] = du[c] + (u0 + a * (u1 - u0));
+            }
+        }
+        else
+        {
+            for (int c = 0; c < NU; c++)
+            {
+                const double u0 = Ub[i * NU + c], u1 = Ub[iu1 * NU + c];
+                double acc = 0.;
+                for (int j = 0; j < NX; j++)
+                {
+                    const double g0 = Gb[(i * NU + c) * NX + j], g1 = Gb[(iu1 * NU + c) * NX + j];
+                    acc += (g0 + a * (g1 - g0)) * dx[j];
+                }
+                un[c] = -acc + (u0 + a * (u1 - u0));
+            }
         }
         bool ufin = true;
         for (int c = 0; c < NU; c++)

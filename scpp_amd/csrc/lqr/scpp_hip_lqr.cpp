@@ -4,6 +4,7 @@
 #include "lqr_kernels.h"
 #include "lqr_riccati_kernel.h"
 #include "lqr_covariance_kernel.h"
+#include "lqr_discrete_kernel.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -46,6 +47,12 @@ struct scpp_hip_lqr_ctx
     double *qf = nullptr, *P = nullptr; // terminal weights (used when have_qf) and P(t_k) of the last Riccati sweep, allocated on request only
     size_t P_cap = 0;                   // doubles allocated behind P
     bool have_qf = false, have_p = false;
+    // discrete sweep (scpp_hip_lqr_compute_gains_discrete): P lands in the buffer above, Phi and Gamma of every segment in two of their own,
+    // allocated by the first keep request
+    double *phi = nullptr, *gam = nullptr;
+    size_t phi_cap = 0, gam_cap = 0;
+    bool have_disc = false;
+    int hold = 0; // scpp_hip_lqr_set_feedback_hold
     int *gstatus = nullptr, *giters = nullptr;
     // covariance sweep (scpp_hip_lqr_propagate_covariance): inputs and outputs are allocated by the first scpp_hip_lqr_set_covariance_inputs,
     // the full S(t_k) by the first keep_cov request
@@ -118,7 +125,7 @@ static bool allFinite(const double *v, size_t n)
 }
 
 // whatever changes the trajectories or replaces the gains: no gains, no P, no covariance
-static void invalidateGains(scpp_hip_lqr_ctx *c) { c->have_gains = c->gains_computed = c->have_p = c->have_cov = false; }
+static void invalidateGains(scpp_hip_lqr_ctx *c) { c->have_gains = c->gains_computed = c->have_p = c->have_disc = c->have_cov = false; }
 
 // a change of weights or parameters: gains the library computed are stale, gains the caller supplied (scpp_hip_lqr_set_gains) stay
 static void invalidateComputedGains(scpp_hip_lqr_ctx *c)
@@ -206,9 +213,9 @@ extern "C"
 const char *scpp_hip_lqr_version(void)
 {
 #ifdef SCPP_HIP_EMU
-    return "scpp_hip_lqr 1 (cpu emulation)";
+    return "scpp_hip_lqr 2 (cpu emulation)";
 #else
-    return "scpp_hip_lqr 1 (gfx950)";
+    return "scpp_hip_lqr 2 (gfx950)";
 #endif
 }
 
@@ -291,7 +298,7 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim};
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -399,7 +406,7 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
     if (rc)
         return rc;
     c->have_gains = c->gains_computed = true;
-    c->have_p = c->have_cov = false;
+    c->have_p = c->have_disc = c->have_cov = false;
     return countOk(c, c->gstatus, size_t(nodes), n_ok);
 }
 
@@ -432,7 +439,7 @@ int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *c, int steps, int keep_
     DeviceGuard guard(c->device);
     const long nodes = long(c->B) * c->K;
     const size_t p_need = size_t(nodes) * c->nx * c->nx;
-    c->have_p = false;
+    c->have_p = c->have_disc = false;
     if (keep_p)
         if (int rc = growTo(c, &c->P, &c->P_cap, p_need))
             return rc;
@@ -459,6 +466,68 @@ int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *c, double *P)
     DeviceGuard guard(c->device);
     CHECK_HIP(hipMemcpyAsync(P, c->P, size_t(c->B) * c->K * c->nx * c->nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_compute_gains_discrete(scpp_hip_lqr_ctx *c, int steps, int keep, int *n_ok)
+{
+    if (!c || steps < 1)
+        return SCPP_E_ARG;
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (long(c->K - 1) * steps > 0x7fffffffL)
+        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
+    DeviceGuard guard(c->device);
+    const long nodes = long(c->B) * c->K;
+    const size_t segs = size_t(c->B) * (c->K - 1);
+    c->have_p = c->have_disc = false;
+    if (keep)
+    {
+        if (int rc = growTo(c, &c->P, &c->P_cap, size_t(nodes) * c->nx * c->nx))
+            return rc;
+        if (int rc = growTo(c, &c->phi, &c->phi_cap, segs * c->nx * c->nx))
+            return rc;
+        if (int rc = growTo(c, &c->gam, &c->gam_cap, segs * c->nx * c->nu))
+            return rc;
+    }
+    int rc = launchKernel(c, [&](auto pl) {
+        using P = decltype(pl);
+        hipLaunchKernelGGL((lqr_discrete_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
+                           (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
+                           (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep ? c->P : (double *)nullptr,
+                           keep ? c->phi : (double *)nullptr, keep ? c->gam : (double *)nullptr);
+    });
+    if (rc)
+        return rc;
+    c->have_gains = c->gains_computed = true;
+    c->have_disc = keep != 0;
+    c->have_cov = false;
+    return countOk(c, c->gstatus, size_t(nodes), n_ok);
+}
+
+int scpp_hip_lqr_download_discrete(scpp_hip_lqr_ctx *c, double *P, double *Phi, double *Gamma)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_disc)
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t B = size_t(c->B), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
+    if (P)
+        CHECK_HIP(hipMemcpyAsync(P, c->P, B * K * nx * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (Phi)
+        CHECK_HIP(hipMemcpyAsync(Phi, c->phi, B * (K - 1) * nx * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (Gamma)
+        CHECK_HIP(hipMemcpyAsync(Gamma, c->gam, B * (K - 1) * nx * nu * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_feedback_hold(scpp_hip_lqr_ctx *c, int mode)
+{
+    if (!c || (mode != 0 && mode != 1))
+        return SCPP_E_ARG;
+    c->hold = mode;
     return SCPP_OK;
 }
 
@@ -710,7 +779,14 @@ int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *c, const double *x_start, const
                                substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
                                (const double *)c->lim, c->lim_rows == 1 ? 0 : LIM_ROW, c->onsat, c->oclip);
         };
-        if (c->have_lim)
+        if (c->hold)
+        {
+            if (c->have_lim)
+                go(lqr_track_kernel<P, true, true>);
+            else
+                go(lqr_track_kernel<P, false, true>);
+        }
+        else if (c->have_lim)
             go(lqr_track_kernel<P, true>);
         else
             go(lqr_track_kernel<P, false>);

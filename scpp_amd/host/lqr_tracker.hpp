@@ -33,12 +33,19 @@ struct lqr_track_result_t
 // differential Riccati equation swept backwards along each trajectory from P(T) = Qf (scpp_hip_lqr_compute_gains_riccati), riccati_steps
 // RKF78 steps per segment; terminal_weights: the diagonal of Qf, empty: LQR.info's terminal_weights if present, else Qf = Q;
 // keep_riccati: P(t_k) is downloaded into LQRTracker::riccati.
+// discrete = true (finite_horizon must then be false): the sampled-data gains of a loop that changes its correction only at the nodes
+// (scpp_hip_lqr_compute_gains_discrete; LQRTracker::setFeedbackHold flies such a loop): the discrete Riccati recursion over the segments'
+// transition matrices from P_{K-1} = Qf (terminal_weights as above), discrete_steps RKF78 steps per segment; keep_discrete: P, Phi and Gamma are
+// downloaded into LQRTracker::discrete_P, discrete_Phi, discrete_Gamma.
 struct lqr_gain_options_t
 {
     bool finite_horizon = false;
     int riccati_steps = 5;
     bool keep_riccati = false;
     std::vector<double> terminal_weights;
+    bool discrete = false;
+    int discrete_steps = 5;
+    bool keep_discrete = false;
 };
 
 // the closed-loop covariance sweep (scpp_hip_lqr_propagate_covariance): dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0, under the gains the tracker
@@ -104,7 +111,24 @@ public:
             t[size_t(b)] = td.t;
         }
         check(scpp_hip_lqr_set_trajectories(ctx, X.data(), U.data(), t.data(), B), "scpp_hip_lqr_set_trajectories");
-        if (opts.finite_horizon)
+        if (opts.finite_horizon && opts.discrete)
+            throw std::invalid_argument("LQRTracker: finite_horizon and discrete are two gain laws, choose one");
+        if (opts.discrete)
+        {
+            std::vector<double> qf = opts.terminal_weights.empty() ? loadTerminalWeights() : opts.terminal_weights;
+            if (!qf.empty() && qf.size() != NX)
+                throw std::invalid_argument("LQRTracker: terminal_weights needs one entry per state");
+            check(scpp_hip_lqr_set_terminal_weights(ctx, qf.empty() ? nullptr : qf.data()), "scpp_hip_lqr_set_terminal_weights");
+            check(scpp_hip_lqr_compute_gains_discrete(ctx, opts.discrete_steps, opts.keep_discrete ? 1 : 0, &n_ok), "scpp_hip_lqr_compute_gains_discrete");
+            if (opts.keep_discrete)
+            {
+                discrete_P.resize(size_t(B) * K * NX * NX);
+                discrete_Phi.resize(size_t(B) * (K - 1) * NX * NX);
+                discrete_Gamma.resize(size_t(B) * (K - 1) * NX * NU);
+                check(scpp_hip_lqr_download_discrete(ctx, discrete_P.data(), discrete_Phi.data(), discrete_Gamma.data()), "scpp_hip_lqr_download_discrete");
+            }
+        }
+        else if (opts.finite_horizon)
         {
             std::vector<double> qf = opts.terminal_weights.empty() ? loadTerminalWeights() : opts.terminal_weights;
             if (!qf.empty() && qf.size() != NX)
@@ -215,6 +239,9 @@ public:
         model->inputLimits(lim.data());
         setInputLimits(lim);
     }
+    // when the loop updates its feedback term (scpp_hip_lqr_set_feedback_hold): false (the default) on every plant step, true: latched at each
+    // node and held over the segment, the loop the discrete gain law designs for.  Stays until it is set again.
+    void setFeedbackHold(bool node) { check(scpp_hip_lqr_set_feedback_hold(ctx, node ? 1 : 0), "scpp_hip_lqr_set_feedback_hold"); }
     // regulator mode (scpp_hip_lqr_set_stop_tolerance) and user-supplied gains [B][K], for LQRAlgorithm::simulate
     void setStopTolerance(double tol) { check(scpp_hip_lqr_set_stop_tolerance(ctx, tol), "scpp_hip_lqr_set_stop_tolerance"); }
     void setGains(const std::vector<feedback_matrix_t> &G)
@@ -319,8 +346,9 @@ public:
     std::array<double, NX> Q{};
     std::array<double, NU> R{};
     std::vector<feedback_matrix_t> gains; // [B][K]
-    std::vector<int32_t> status, iterations; // iterations: sign iterations, or RKF78 steps behind the node (finite horizon)
+    std::vector<int32_t> status, iterations; // iterations: sign iterations, or RKF78 steps behind the node (finite horizon, discrete)
     std::vector<double> riccati;             // [B][K][NX][NX], finite horizon with keep_riccati only
+    std::vector<double> discrete_P, discrete_Phi, discrete_Gamma; // [B][K][NX][NX], [B][K-1][NX][NX], [B][K-1][NX][NU]: discrete with keep_discrete only
     lqr_gain_options_t opts;
 
 private:

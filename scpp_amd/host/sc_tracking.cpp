@@ -3,8 +3,12 @@
 //                         flown along it from x_init                                              (what the reference does)
 //   --batch N [--seed S]: N randomised initial states: N trajectories, N x K gains, N flights from those initial states
 //   --config DIR --out DIR --K n --device d --time-step s
-//   --gains frozen|riccati : frozen (default): one frozen-time infinite-horizon gain per node (the reference's); riccati: finite-horizon gains,
+//   --gains frozen|riccati|discrete : frozen (default): one frozen-time infinite-horizon gain per node (the reference's); riccati: finite-horizon gains,
 //                         the differential Riccati equation swept backwards along each trajectory; --riccati-steps n RKF78 steps per segment (5)
+//                         discrete: sampled-data gains, the discrete Riccati recursion over the segments' transition matrices
+//                         (scpp_hip_lqr_compute_gains_discrete); --discrete-steps n RKF78 steps per segment (5)
+//   --hold step|node    : step (default): the feedback term changes on every plant step; node: it is latched at each node and held over the
+//                         segment (scpp_hip_lqr_set_feedback_hold), the loop --gains discrete designs for
 //   --covariance        : also the closed-loop covariance sweep along every trajectory under those gains (scpp_hip_lqr_propagate_covariance):
 //                         S(0) = diag(initial_std)^2 and W = diag(disturbance_std)^2 from the optional vectors initial_std / disturbance_std of
 //                         LQR.info (absent: 0); --covariance-steps n RKF78 steps per segment (5).  Writes state_std.txt (one node per row) and
@@ -39,7 +43,7 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
-    bool covariance = false, saturate = false;
+    bool covariance = false, saturate = false, hold_node = false;
     int covariance_steps = 5, samples = 1;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
@@ -70,12 +74,25 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--gains"))
         {
             const std::string which = next();
-            if (which != "frozen" && which != "riccati")
+            if (which != "frozen" && which != "riccati" && which != "discrete")
             {
-                std::fprintf(stderr, "--gains %s: frozen or riccati\n", which.c_str());
+                std::fprintf(stderr, "--gains %s: frozen, riccati or discrete\n", which.c_str());
                 return 2;
             }
             gain_opts.finite_horizon = which == "riccati";
+            gain_opts.discrete = which == "discrete";
+        }
+        else if (!std::strcmp(argv[i], "--discrete-steps"))
+            gain_opts.discrete_steps = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--hold"))
+        {
+            const std::string which = next();
+            if (which != "step" && which != "node")
+            {
+                std::fprintf(stderr, "--hold %s: step or node\n", which.c_str());
+                return 2;
+            }
+            hold_node = which == "node";
         }
         else if (!std::strcmp(argv[i], "--riccati-steps"))
             gain_opts.riccati_steps = std::atoi(next());
@@ -136,6 +153,9 @@ int main(int argc, char **argv)
         if (gain_opts.finite_horizon)
             std::printf("Gains: riccati (finite horizon, %d RKF78 steps per segment, %zu Riccati right-hand sides)\n", gain_opts.riccati_steps,
                         N * (r.td[0].n_X() - 1) * size_t(gain_opts.riccati_steps) * 13);
+        else if (gain_opts.discrete)
+            std::printf("Gains: discrete (sampled data, %d RKF78 steps per segment, %zu transition right-hand sides)\n", gain_opts.discrete_steps,
+                        N * (r.td[0].n_X() - 1) * size_t(gain_opts.discrete_steps) * 13);
         else
             std::printf("Gains: frozen (one infinite-horizon gain per node)\n");
         std::printf("Time, LQR gains: %.2f ms for %zu nodes (%d converged): %.0f gains/s (with context set-up and transfers)\n", 1e3 * t_gains, nodes,
@@ -176,6 +196,7 @@ int main(int argc, char **argv)
         const size_t F = x_starts.size();
         if (saturate)
             tracker.setInputLimitsFromModel();
+        tracker.setFeedbackHold(hold_node);
 
         // start simulation
         scpp::lqr_track_result_t sim;
@@ -193,6 +214,8 @@ int main(int argc, char **argv)
         std::sort(rel.begin(), rel.end());
         std::printf("Simulating %zu trajectories.\nFinished after %d steps (instance 0), %ld plant steps in %.2f ms: %.0f steps/s; %d of %zu flights finite\n", N,
                     sim.steps[0] + 1, steps, 1e3 * t_run, double(steps) / t_run, sim.n_finite, F);
+        std::printf("Hold: %s\n", hold_node ? "node (the feedback term is latched at each node and held over the segment)"
+                                            : "step (the feedback term changes on every plant step)");
         if (samples > 1)
             std::printf("Sample fan: %d flights per trajectory, %zu flights\n", samples, F);
         if (saturate)

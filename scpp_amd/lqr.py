@@ -70,13 +70,17 @@ class LQRTracker:
     horizon="infinite" (the default, the reference's): one frozen-time gain per node, each from an algebraic Riccati equation of its own.
     horizon="finite": the differential Riccati equation swept backwards along each trajectory from P(T) = Qf (terminal_weights, the
     diagonal; None: LQR.info's terminal_weights if present, else Qf = Q), riccati_steps RKF78 steps per segment; keep_riccati=True also
-    keeps P(t_k) (the `riccati` property, [B][K][nx][nx])."""
+    keeps P(t_k) (the `riccati` property, [B][K][nx][nx]).
+    horizon="discrete": the gains of a loop that changes its correction only at the nodes and holds it over a segment (track(hold="node")
+    flies it): the discrete Riccati recursion over the segments' transition matrices [Phi | Gamma], from P_{K-1} = Qf as above, with stage
+    weights Q dt and R dt, discrete_steps RKF78 steps per segment; keep_discrete=True also keeps P, Phi and Gamma (discrete())."""
 
     def __init__(self, model, X, U, t, state_weights=None, input_weights=None, par=None, device=0, library=None, compute=True,
-                 horizon="infinite", terminal_weights=None, riccati_steps=5, keep_riccati=False):
-        if horizon not in ("infinite", "finite"):
-            raise ValueError(f"horizon = {horizon!r}: 'infinite' or 'finite'")
+                 horizon="infinite", terminal_weights=None, riccati_steps=5, keep_riccati=False, discrete_steps=5, keep_discrete=False):
+        if horizon not in ("infinite", "finite", "discrete"):
+            raise ValueError(f"horizon = {horizon!r}: 'infinite', 'finite' or 'discrete'")
         self.horizon, self.riccati_steps, self.keep_riccati = horizon, int(riccati_steps), bool(keep_riccati)
+        self.discrete_steps, self.keep_discrete = int(discrete_steps), bool(keep_discrete)
         self.model = model
         nx, nu = model.state_dim, model.input_dim
         X = np.asarray(X, dtype=np.float64)
@@ -93,11 +97,11 @@ class LQRTracker:
         self.ctx = LqrContext(model.model_id, self.K, self.B, self.foh, device, library)
         self.ctx.set_weights(self.Q, self.R)
         self.Qf = None
-        if horizon == "finite":
+        if horizon in ("finite", "discrete"):
             qf = load_lqr_terminal_weights(model) if terminal_weights is None else terminal_weights
             self.Qf = self.Q.copy() if qf is None else np.asarray(qf, dtype=np.float64)
             self.ctx.set_terminal_weights(self.Qf)
-        self._riccati = None
+        self._riccati = self._discrete = None
         self.ctx.set_flow_params(si_flow_params(model) if par is None else par)
         self.ctx.set_trajectories(self.X, self.U, self.t)
         self._gains = None
@@ -115,9 +119,11 @@ class LQRTracker:
     def computeGains(self):
         if self.horizon == "finite":
             return self.computeGainsRiccati()
+        if self.horizon == "discrete":
+            return self.computeGainsDiscrete()
         self.n_ok = self.ctx.compute_gains()
         self._gains = self.ctx.download_gains()
-        self._riccati = None
+        self._riccati = self._discrete = None
         return self.n_ok
 
     def computeGainsRiccati(self, steps=None, keep=None):
@@ -127,7 +133,25 @@ class LQRTracker:
         self.n_ok = self.ctx.compute_gains_riccati(steps, keep)
         self._gains = self.ctx.download_gains()
         self._riccati = self.ctx.download_riccati() if keep else None
+        self._discrete = None
         return self.n_ok
+
+    def computeGainsDiscrete(self, steps=None, keep=None):
+        """sampled-data gains of every trajectory (one discrete Riccati recursion each, on the device); they replace the gains held so far"""
+        steps = self.discrete_steps if steps is None else int(steps)
+        keep = self.keep_discrete if keep is None else bool(keep)
+        self.n_ok = self.ctx.compute_gains_discrete(steps, keep)
+        self._gains = self.ctx.download_gains()
+        self._discrete = self.ctx.download_discrete() if keep else None
+        self._riccati = None
+        return self.n_ok
+
+    def discrete(self):
+        """dict of P [B][K][nx][nx], Phi [B][K-1][nx][nx], Gamma [B][K-1][nx][nu] of the last discrete sweep; needs keep_discrete=True (or
+        computeGainsDiscrete(keep=True))"""
+        if self._discrete is None:
+            raise RuntimeError("no discrete sweep kept: construct with horizon='discrete', keep_discrete=True")
+        return self._discrete
 
     @property
     def riccati(self):
@@ -139,7 +163,7 @@ class LQRTracker:
     def setGains(self, G):
         """user-supplied gains [B][K][nu][nx] instead of the computed ones"""
         self.ctx.set_gains(G)
-        self._riccati = None
+        self._riccati = self._discrete = None
         self._gains = dict(gains=np.array(G, dtype=np.float64).reshape(self.B, self.K, self.model.input_dim, self.model.state_dim), status=None, iters=None)
 
     @property
@@ -175,11 +199,16 @@ class LQRTracker:
             lim = model_input_limits(self.model)
         self.ctx.set_input_limits(lim)
 
-    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30, samples=1):
+    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30, samples=1, hold="step"):
         """The loop of SC_tracking.cpp:48-75 on the device, `samples` flights per trajectory from x_start [B * samples][nx] (flight f follows
         trajectory f // samples; samples = 1: one flight per trajectory).  Returns x, u, t, steps, status, err0, err1 (|x - x_final| at
         start / end), max_dev (largest |x - x_ref|), n_sat (plant steps on which the input limits clipped), max_clip (largest
-        |u_cmd - u|; both 0 without limits), n_finite and, with n_record > 0, `record` (of the first n_record flights)."""
+        |u_cmd - u|; both 0 without limits), n_finite and, with n_record > 0, `record` (of the first n_record flights).
+        hold="step" (the default): the feedback term changes on every plant step; hold="node": du = -G[i] (x - x_ref) is latched at the
+        first plant step of segment i and held over it (the loop horizon="discrete" designs for)."""
+        if hold not in ("step", "node"):
+            raise ValueError(f"hold = {hold!r}: 'step' or 'node'")
+        self.ctx.set_feedback_hold(1 if hold == "node" else 0)
         x_final = self.model.p.x_final if x_final is None else x_final
         x_final = np.array(list(x_final), dtype=np.float64)
         if max_steps is None:

@@ -1,7 +1,7 @@
 """LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
-    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--out FILE]
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
 segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
@@ -20,7 +20,12 @@ of flights with n_sat > 0, and the final errors with and without limits on the s
 frozen-time gains, without limits unless --saturate is given too: flight 0 of a trajectory starts where the trajectory was solved from, the
 others 1 % (Gaussian, fixed seed) off that state.  It only ADDS the key samples_legs, one entry per N.
 
-The flight call of these two legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
+--discrete STEPS (measure(discrete=STEPS)) adds, after every other leg, the sampled-data gains: one discrete Riccati recursion per trajectory
+(STEPS RKF78 steps per segment for the transition matrices), then the N flights of the default leg under those gains with the feedback term
+held over a segment (track(hold="node")).  It only ADDS keys (discrete_*): the sweep's wall time, transition right-hand sides/s, the status
+counts and the flights.
+
+The flight call of the saturate and samples legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
 best of --repeat.
 """
 import argparse
@@ -36,7 +41,7 @@ import numpy as np  # noqa: E402
 import scpp_amd  # noqa: E402
 
 
-def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=()):
+def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -67,6 +72,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
     ric = riccati_leg(trk, x0, int(riccati), repeat) if riccati else {}
     if covariance:
         ric.update(covariance_leg(trk, int(covariance), repeat, "riccati" if riccati else "frozen"))
+    if discrete:
+        ric.update(discrete_leg(trk, x0, int(discrete), repeat))
     trk.close()
     fin = out["status"] != -2
     e = out["err1"][fin]
@@ -175,6 +182,41 @@ def riccati_leg(trk, x0, steps, repeat):
     }
 
 
+def discrete_leg(trk, x0, steps, repeat):
+    """sampled-data gains on the tracker's trajectories, then the default leg's flights under them with the feedback term held over a segment"""
+    trk.ctx.compute_gains_discrete(steps)  # warm
+    td = []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        n_ok = trk.ctx.compute_gains_discrete(steps)  # returns after the status of every node is on the host
+        td.append(time.perf_counter() - t)
+    trk.computeGainsDiscrete(steps, keep=False)
+    st, it = trk.status, trk.iterations
+    tt = []
+    for _ in range(repeat):
+        t = time.perf_counter()
+        out = trk.track(x0, hold="node")
+        tt.append(time.perf_counter() - t)
+    trk.ctx.set_feedback_hold(0)
+    fin = out["status"] != -2
+    e = out["err1"][fin]
+    # RocketQuat integrates every segment twice (Phi, then Gamma): two Jacobian evaluations and two tile products per counted right-hand side
+    rhs = trk.B * (trk.K - 1) * steps * 13
+    return {
+        "discrete_steps_per_segment": steps, "discrete_wall_s": min(td), "discrete_rhs": int(rhs), "discrete_rhs_per_s": rhs / min(td),
+        "discrete_nodes": int(st.size), "discrete_status_ok": int(n_ok), "discrete_status_nonfinite": int((st == -2).sum()),
+        "discrete_status_other": int(((st != 0) & (st != -2)).sum()), "discrete_gains_nonfinite_values": int((~np.isfinite(trk.gains)).sum()),
+        "discrete_steps_behind_node0": int(it[:, 0].max()),
+        "discrete_hold": "node", "discrete_track_wall_s": min(tt), "discrete_tracked_plant_steps": int(out["steps"].sum()),
+        "discrete_tracked_plant_steps_per_s": float(out["steps"].sum() / min(tt)),
+        "discrete_flights_finite": int(out["n_finite"]), "discrete_flights_completed": int((out["status"] == 0).sum()),
+        "discrete_flights_step_cap": int((out["status"] == 1).sum()), "discrete_flights_nonfinite": int((out["status"] == -2).sum()),
+        "discrete_output_nonfinite_values": int(sum((~np.isfinite(out[k])).sum() for k in ("x", "u", "t", "err0", "err1", "max_dev"))),
+        "discrete_final_error_p5_p50_p95": [float(v) for v in np.percentile(e, [5, 50, 95])] if e.size else [],
+        "discrete_max_excursion_p50": float(np.median(out["max_dev"][fin])) if fin.any() else None,
+    }
+
+
 def covariance_leg(trk, steps, repeat, law):
     """the closed-loop covariance sweep on the tracker's trajectories under the gains it holds"""
     sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
@@ -214,10 +256,11 @@ if __name__ == "__main__":
     ap.add_argument("--covariance", type=int, default=0, help="RKF78 steps per segment of the covariance leg (0: no such leg)")
     ap.add_argument("--saturate", action="store_true", help="the flights again with the model's input limits in the loop")
     ap.add_argument("--samples", default="", help="comma-separated flights per trajectory of the sample-fan legs, e.g. 1,4,16")
+    ap.add_argument("--discrete", type=int, default=0, help="RKF78 steps per segment of the sampled-data leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
-                  samples=[int(v) for v in a.samples.split(",") if v])
+                  samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete)
     line = json.dumps(res)
     print(line)
     if a.out:
