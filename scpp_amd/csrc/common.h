@@ -282,4 +282,29 @@ constexpr double RK_A[RK_S][RK_S] = {
     {-1777. / 4100., 0., 0., -341. / 164., 4496. / 1025., -289. / 82., 2193. / 4100., 51. / 82., 33. / 164., 12. / 41., 0., 1.}};
 constexpr double RK_B[RK_S] = {0., 0., 0., 0., 0., 34. / 105., 9. / 35., 9. / 35., 9. / 280., 9. / 280., 0., 41. / 840., 41. / 840.};
 
+// A stage is LIVE if its slope is read at all: by the 8th-order weights or by a later stage.  Stage 10 is not (it belongs to the embedded
+// 7th-order estimate, which nothing here propagates): RK_SKIP_DEAD leaves its evaluation out of the segment integration, the cost step and
+// simulate_kernel.  The slopes of the other stages, and so every result, stay bit for bit what they are.
+#ifndef RK_SKIP_DEAD
+#define RK_SKIP_DEAD 1
+#endif
+constexpr bool rkStageLive(int s)
+{
+    if (RK_B[s] != 0.)
+        return true;
+    for (int r = s + 1; r < RK_S; r++)
+        if (RK_A[r][s] != 0.)
+            return true;
+    return false;
+}
+// live stages among 0 .. s-1
+constexpr int rkLiveBefore(int s)
+{
+    int n = 0;
+    for (int j = 0; j < s; j++)
+        n += rkStageLive(j) ? 1 : 0;
+    return n;
+}
+static_assert(rkLiveBefore(RK_S) == RK_S - 1 && !rkStageLive(10), "RKF78 with the 8th-order weights: exactly one dead stage, index 10");
+
 } // namespace scpp

@@ -66,6 +66,18 @@ constexpr int DISC_STEPS_MAX = 5;
 #define DISC_WAVES_PER_SIMD 2
 #endif
 
+// Stage schedule of the segment integration.  0: the round-1 structure, five wavefront barriers per stage (discretizeSegment); kept as the
+// structure the regression test compares against, and what a context created under SCPP_DISC_SCHEDULE=0 launches, with all 13 stages.
+// 1: three barriers per stage, the per-call set-up outside the segment loop (discretizeSetup + discretizeSegmentBody below).  Same arithmetic,
+// entry by entry.  The forward-mode-AD path has schedule 0 only.
+#ifndef DISC_STAGE_SCHEDULE
+#define DISC_STAGE_SCHEDULE 1
+#endif
+#ifdef DISC_AD_JACOBIAN
+#undef DISC_STAGE_SCHEDULE
+#define DISC_STAGE_SCHEDULE 0
+#endif
+
 template <class Model, bool FOH, bool VT>
 struct DiscLayout
 {
@@ -95,6 +107,9 @@ struct DiscLds
 {
     using L = DiscLayout<Model, FOH, VT>;
     __attribute__((aligned(16))) double Ys[32 * L::NX + 2];
+#if DISC_STAGE_SCHEDULE
+    __attribute__((aligned(16))) double Ys1[32 * L::NX + 2]; // stage values of every other live stage (schedule 1)
+#endif
 #ifdef DISC_AD_JACOBIAN
     __attribute__((aligned(16))) double Jm[L::NX * L::NJP]; // [sigma*A | sigma*B] row-major
     double fv[L::NX];                                       // f(x,u) (unscaled)
@@ -108,7 +123,8 @@ struct DiscLds
 
 // The integration of ONE segment by one wavefront: the body of discretize_kernel, and of the discretisation step of the persistent SCvx
 // kernel (scvx_persistent.h), where one wavefront walks through the K - 1 segments of its instance.
-template <class Model, bool FOH, bool VT>
+// This is stage schedule 0 (DISC_STAGE_SCHEDULE above); SKIP leaves the dead stage out.
+template <class Model, bool FOH, bool VT, bool SKIP = (RK_SKIP_DEAD != 0)>
 __device__ __forceinline__ void discretizeSegment(int B, int K, const double *__restrict__ X, const double *__restrict__ U,
                                                   const double *__restrict__ sigma, const double *__restrict__ par, int par_stride,
                                                   const int *__restrict__ active, double *__restrict__ Aout, double *__restrict__ Bout,
@@ -293,6 +309,8 @@ __device__ __forceinline__ void discretizeSegment(int B, int K, const double *__
         // dynamically, i.e. from scratch memory, and tests the coefficients at run time).
         forEachStage([&](auto sc) {
             constexpr int s = decltype(sc)::value;
+            if (SKIP && !rkStageLive(s))
+                return; // its slope is never read (common.h)
             // ---- stage value ys = y + h * sum_j a_sj k_j ----
 #ifdef DISC_PROFILE
             const long long p0 = clock64();
@@ -571,7 +589,392 @@ __device__ __forceinline__ void discretizeSegment(int B, int K, const double *__
     }
 }
 
+#if DISC_STAGE_SCHEDULE
+// ---- schedule 1 ----
+// A stage of schedule 0 is a chain of five LDS round trips: stage value -> (read the state column back, hoists, one lane writes) -> table pass 0
+// -> table pass 1 -> operands, product -> barrier in front of the next stage's writes.  Here
+//   * the hoists (Model::JacobianTable::evalHoists: an IEEE 1 / m for RocketQuat) are evaluated on the state column's entries taken from the
+//     registers of the lanes that own them (v_readlane), and written with u(t) and the input-only terms together with the stage value: one
+//     barrier in front of table pass 0 instead of two;
+//   * consecutive live stages write their stage values into alternate copies of Ys (Ys / Ys1), so a stage's operand reads need no barrier in
+//     front of the next stage's writes: what the next stage writes before ITS first barrier (the other Ys copy, W_X, W_U, W_UAUX, W_H) is read
+//     by this stage only before its last barrier (the table passes), and what this stage reads after its last barrier (W_J, W_F, its Ys copy) is
+//     written again only after the next stage's first barrier;
+//   * what does not depend on the segment is done once per call (discretizeSetup): the zero fills, the parameter operands and prepare(), and the
+//     lane's two table slots (40 loads from constant tables) -- the persistent kernels call it once for the K - 1 segments of an instance.  The
+//     solver overwrites that LDS region between two calls, so nothing of it may be kept across calls.
+// Every entry goes through the operations of schedule 0 in the same order.
+template <class Model>
+struct DiscTableSlots
+{
+    using TB = typename Model::JacobianTable;
+    double tcf[2][TB::MAXMON];         // coefficients
+    unsigned tof[2][TB::MAXMON][2];    // LDS byte offsets of the factors (two 16-bit offsets per word)
+    int ttg[2];                        // target index in W, -1: idle slot
+};
+
+// false: nothing to do for this instance (beyond the batch, or inactive)
 template <class Model, bool FOH, bool VT>
+__device__ __forceinline__ bool discretizeSetup(int B, const double *__restrict__ par, int par_stride, const int *__restrict__ active, const long inst,
+                                                DiscLds<Model, FOH, VT> *lds, DiscTableSlots<Model> &ts)
+{
+    using L = DiscLayout<Model, FOH, VT>;
+    using TB = typename Model::JacobianTable;
+    constexpr int NX = L::NX, NU = L::NU, NP = L::NP, NAUX = Model::JacobianRows::NAUX;
+    static_assert(NX <= 16 && L::NCOLS + L::NG <= 32 && L::NG == 4, "one 16-row tile of states, two 16-column tiles of V");
+    const int lane = threadIdx.x;
+    if (inst >= B)
+        return false;
+    if (active && active[inst] == 0)
+        return false;
+    for (int i = lane; i < 32 * NX + 2; i += WAVE)
+    {
+        lds->Ys[i] = 0.;
+        lds->Ys1[i] = 0.;
+    }
+    for (int i = lane; i < TB::NW; i += WAVE)
+        lds->Wt[i] = (i == TB::W_ONE) ? 1. : 0.;
+    WAVE_SYNC();
+    if (lane == 0)
+    {
+        double p[NP], aux0[NAUX];
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+            p[i] = par[inst * par_stride + i];
+        Model::JacobianRows::prepare(p, aux0);
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+        {
+            lds->cst[i] = p[i];
+            lds->Wt[TB::W_PAR + i] = p[i];
+        }
+#pragma unroll
+        for (int i = 0; i < NAUX; i++)
+        {
+            lds->cst[NP + 2 * NU + i] = aux0[i];
+            lds->Wt[TB::W_AUX + i] = aux0[i];
+        }
+    }
+#pragma unroll
+    for (int ps = 0; ps < 2; ps++)
+    {
+        const int slot = ps * 64 + lane;
+        ts.ttg[ps] = TB::target(slot);
+#pragma unroll
+        for (int q = 0; q < TB::MAXMON; q++)
+        {
+            ts.tcf[ps][q] = TB::coef(slot, q);
+            ts.tof[ps][q][0] = unsigned(TB::factor(slot, q, 0) * 8) | (unsigned(TB::factor(slot, q, 1) * 8) << 16);
+            ts.tof[ps][q][1] = unsigned(TB::factor(slot, q, 2) * 8) | (unsigned(TB::factor(slot, q, 3) * 8) << 16);
+        }
+    }
+    WAVE_SYNC();
+    return true;
+}
+
+// One segment after discretizeSetup.  SKIP: leave the dead stage out (12 live stages per step: the Ys copy of a stage is a compile-time fact).
+template <class Model, bool FOH, bool VT, bool SKIP>
+__device__ __forceinline__ void discretizeSegmentBody(int K, const double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ sigma,
+                                                      double *__restrict__ Aout, double *__restrict__ Bout, double *__restrict__ Cout,
+                                                      double *__restrict__ Sout, double *__restrict__ Zout, int steps_opt, const long inst, const int k,
+                                                      DiscLds<Model, FOH, VT> *lds, const DiscTableSlots<Model> &ts)
+{
+    using L = DiscLayout<Model, FOH, VT>;
+    using TB = typename Model::JacobianTable;
+    constexpr int NX = L::NX, NU = L::NU, NP = L::NP, NJ = L::NJ, NCOLS = L::NCOLS, NG = L::NG, EPL = L::EPL;
+    constexpr int NAUX = Model::JacobianRows::NAUX, NUAUX = Model::JacobianRows::NUAUX, UHP = NUAUX + 1 + NU;
+    constexpr int NLIVE = SKIP ? rkLiveBefore(RK_S) : RK_S;
+    auto &Ys = lds->Ys;
+    auto &uh = lds->uh;
+    auto &Wt = lds->Wt;
+    auto &cst = lds->cst;
+    (void)NAUX;
+
+    const int lane = threadIdx.x;
+    const int nseg = K - 1;
+    const double sg = sigma[inst];
+    const double dt = VT ? 1. / double(K - 1) : sg / double(K - 1);
+    const double tscale = VT ? sg : 1.;
+    int nsteps = DISC_STEPS > 0 ? DISC_STEPS : steps_opt; // scpp_hip_set_discretization_steps: 0 = the rule, 1 .. 5 = pinned
+    if (nsteps <= 0)
+    {
+        const double seg_seconds = fabs(sg) / double(K - 1);
+        nsteps = int(ceil(seg_seconds / DISC_MAX_STEP));
+        nsteps = nsteps < 1 ? 1 : (nsteps > DISC_STEPS_MAX ? DISC_STEPS_MAX : nsteps);
+    }
+    nsteps = uniformInt(nsteps);
+    double u0[NU], u1[NU];
+#pragma unroll
+    for (int i = 0; i < NU; i++)
+    {
+        u0[i] = U[(inst * K + k) * NU + i];
+        u1[i] = FOH ? U[(inst * K + k + 1) * NU + i] : u0[i];
+    }
+    if (lane == 0)
+    {
+#pragma unroll
+        for (int i = 0; i < NU; i++)
+        {
+            cst[NP + i] = u0[i];
+            cst[NP + NU + i] = u1[i];
+        }
+    }
+    {
+        // u(t) at each of the nsteps x 13 stage times and what the rows need of it alone, one stage time per lane (the parameters: from the set-up)
+        double p[NP];
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+            p[i] = cst[i];
+        const double hh = dt / double(nsteps);
+        for (int e = lane; e < nsteps * RK_S; e += WAVE)
+        {
+            const double tse = double(e / RK_S) * hh + RK_C[e % RK_S] * hh;
+            const double fre = FOH ? tse / dt : 0.;
+            double ue[NU], ua[NUAUX];
+#pragma unroll
+            for (int i = 0; i < NU; i++)
+                ue[i] = u0[i] + fre * (u1[i] - u0[i]);
+            Model::JacobianRows::prepareInput(ue, p, ua);
+#pragma unroll
+            for (int i = 0; i < NUAUX; i++)
+                uh[e * UHP + i] = ua[i];
+            uh[e * UHP + NUAUX] = fre;
+#pragma unroll
+            for (int i = 0; i < NU; i++)
+                uh[e * UHP + NUAUX + 1 + i] = ue[i];
+        }
+    }
+    WAVE_SYNC();
+
+    const int row = lane & 15, g = lane >> 4;
+    const bool lane_on = row < NX;
+#ifndef SCPP_HIP_EMU
+    __builtin_assume(g >= 0 && g < NG);
+#endif
+    const double x0r = lane_on ? X[(inst * K + k) * NX + row] : 0.;
+    double y[EPL];
+    bool eon[EPL];
+#pragma unroll
+    for (int m = 0; m < EPL; m++)
+    {
+        const int c = m * NG + g;
+        eon[m] = lane_on && c < NCOLS;
+        double v = 0.;
+        if (c == 0)
+            v = x0r;
+        else if (c >= L::COL_PHI && c < L::COL_PHI + NX)
+            v = (c - L::COL_PHI == row) ? 1. : 0.;
+        y[m] = eon[m] ? v : 0.;
+    }
+
+    double kk[RK_S][EPL];
+    const double h = dt / double(nsteps);
+    for (int step = 0; step < nsteps; step++)
+    {
+        forEachStage([&](auto sc) {
+            constexpr int s = decltype(sc)::value;
+            if (SKIP && !rkStageLive(s))
+                return; // its slope is never read (common.h)
+            constexpr int ord = SKIP ? rkLiveBefore(s) : s;
+            const int buf = (NLIVE % 2 == 0) ? (ord & 1) : ((ord + step) & 1);
+            double *Yb = buf ? lds->Ys1 : lds->Ys;
+            const int e = step * RK_S + s;
+            // ---- stage value ys = y + h * sum_j a_sj k_j, and every operand of the Jacobian table that changes with the stage ----
+            double ys0 = 0.;
+#pragma unroll
+            for (int m = 0; m < EPL; m++)
+            {
+                double acc = 0.;
+#pragma unroll
+                for (int j = 0; j < s; j++)
+                    if (RK_A[s][j] != 0.)
+                        acc += RK_A[s][j] * kk[j][m];
+                const double ys = y[m] + h * acc;
+                if (eon[m])
+                    Yb[(m * NG + g) * NX + row] = ys;
+                if (m == 0)
+                {
+                    ys0 = ys;
+                    if (g == 0 && lane_on)
+                        Wt[TB::W_X + row] = ys; // the state column is also operand x of the Jacobian table
+                }
+            }
+            {
+                // the state column from the lanes (g = 0, row < NX) that hold it: no round trip through Ys; unused entries cost nothing
+                double xs[NX], hh[TB::NH];
+#pragma unroll
+                for (int i = 0; i < NX; i++)
+                    xs[i] = readLane(ys0, i);
+                TB::evalHoists(xs, uh + e * UHP + NUAUX + 1, cst, cst + NP + 2 * NU, uh + e * UHP, hh);
+                if (lane == 0)
+                {
+#pragma unroll
+                    for (int i = 0; i < TB::NH; i++)
+                        Wt[TB::W_H + i] = hh[i];
+                }
+                if (lane < NU)
+                    Wt[TB::W_U + lane] = uh[e * UHP + NUAUX + 1 + lane];
+                else if (lane < NU + NUAUX)
+                    Wt[TB::W_UAUX + lane - NU] = uh[e * UHP + lane - NU];
+            }
+            WAVE_SYNC();
+            const double frac = FOH ? uh[e * UHP + NUAUX] : 0.; // t / dt, tabulated with the input
+            const char *wb = reinterpret_cast<const char *>(Wt);
+#pragma unroll
+            for (int ps = 0; ps < 2; ps++)
+            {
+                double val = 0.;
+#pragma unroll
+                for (int q = 0; q < (ps == 0 ? TB::MAXMON : TB::MAXMON_B); q++)
+                {
+                    const double f0 = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][0] & 0xFFFFu));
+                    const double f1 = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][0] >> 16));
+                    const double f2 = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][1] & 0xFFFFu));
+                    const double f3 = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][1] >> 16));
+                    val += ((ts.tcf[ps][q] * f0) * f1) * (f2 * f3);
+                }
+                if (ts.ttg[ps] >= 0)
+                    Wt[ts.ttg[ps]] = val;
+                WAVE_SYNC();
+            }
+            const int rowc = lane_on ? row : 0;
+            double bsel[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                const double v = Wt[TB::W_J + rowc * NJ + (4 * t + g < NX ? 4 * t + g : 0)];
+                bsel[t] = (4 * t + g < NX) ? v : 0.; // columns >= NX belong to the inputs
+            }
+            const double fr = Wt[TB::W_F + rowc]; // f[row] (unscaled)
+            // ---- derivative of the owned entries: d(row, c) = J[row,:] V[:,c] + forcing(row, c), branch-free ----
+            const double alphaB = FOH ? (1. - frac) : 1.;
+            d4_t acc0 = {0., 0., 0., 0.}, acc1 = {0., 0., 0., 0.};
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                const int kx = g + 4 * t; // contraction index = state j
+                const double b = bsel[t] * tscale; // sigma scaling of A applied to the four entries this lane contributes
+                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Yb[row * NX + kx], b, acc0, 0, 0, 0);
+                if (NCOLS > 16)
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Yb[(16 + row) * NX + kx], b, acc1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int m = 0; m < EPL; m++)
+            {
+                const int c = m * NG + g;
+                const double acc = m < 4 ? acc0[m < 4 ? m : 0] : acc1[m >= 4 ? m - 4 : 0];
+                // forcing: B columns J[row, NX+j] * alpha ; C columns J[row, NX+j] * frac ; s column f ; x column: sigma f only
+                double d = acc;
+                const bool slotB = m * NG < L::COL_B + NU && m * NG + NG > L::COL_B;
+                const bool slotC = FOH && m * NG < L::COL_C + NU && m * NG + NG > L::COL_C;
+                if (slotB || slotC)
+                {
+                    const bool isB = c >= L::COL_B && c < L::COL_B + NU;
+                    const bool isC = FOH && c >= L::COL_C && c < L::COL_C + NU;
+                    const int jj = isB ? c - L::COL_B : isC ? c - L::COL_C : 0;
+                    const double w = isB ? alphaB : isC ? frac : 0.;
+                    const double jb = Wt[TB::W_J + rowc * NJ + NX + jj]; // J[row, NX + jj], jj is lane dependent
+                    d += (w * tscale) * jb;                              // sigma scaling of B
+                }
+                if (VT && m * NG <= L::COL_S && m * NG + NG > L::COL_S)
+                    d = (c == L::COL_S) ? d + fr : d;
+                if (m == 0)
+                    d = (c == 0) ? tscale * fr : d;
+                kk[s][m] = d;
+            }
+            // no barrier here: the next live stage writes the other copy of Ys
+        });
+        // ---- y += h * sum_s b_s k_s ----
+#pragma unroll
+        for (int m = 0; m < EPL; m++)
+        {
+            double acc = 0.;
+#pragma unroll
+            for (int s = 0; s < RK_S; s++)
+                if (RK_B[s] != 0.)
+                    acc += RK_B[s] * kk[s][m];
+            y[m] += h * acc;
+        }
+    }
+    WAVE_SYNC(); // the last stage's operand reads before the result goes through Ys
+
+    // ---- write A_k, B_k, C_k, s_k ; z_k from the affine identity ----
+    const long seg = inst * nseg + k;
+#pragma unroll
+    for (int m = 0; m < EPL; m++)
+    {
+        const int c = m * NG + g;
+        if (!eon[m])
+            continue;
+        Ys[c * NX + row] = y[m];
+        if (c >= L::COL_PHI && c < L::COL_PHI + NX)
+            Aout[seg * NX * NX + row * NX + (c - L::COL_PHI)] = y[m];
+        else if (c >= L::COL_B && c < L::COL_B + NU)
+            Bout[seg * NX * NU + row * NU + (c - L::COL_B)] = y[m];
+        else if (FOH && c >= L::COL_C && c < L::COL_C + NU)
+            Cout[seg * NX * NU + row * NU + (c - L::COL_C)] = y[m];
+        else if (VT && c == L::COL_S)
+            Sout[seg * NX + row] = y[m];
+    }
+    // stash x0 behind the integrated columns for the identity
+    if (lane < NX)
+        Ys[NCOLS * NX + lane] = x0r;
+    WAVE_SYNC();
+    if (lane < NX)
+    {
+        double z = Ys[lane]; // x(dt)
+#pragma unroll
+        for (int j = 0; j < NX; j++)
+            z -= Ys[(L::COL_PHI + j) * NX + lane] * Ys[NCOLS * NX + j];
+#pragma unroll
+        for (int j = 0; j < NU; j++)
+        {
+            z -= Ys[(L::COL_B + j) * NX + lane] * u0[j];
+            if (FOH)
+                z -= Ys[(L::COL_C + j) * NX + lane] * u1[j];
+        }
+        if (VT)
+            z -= Ys[L::COL_S * NX + lane] * sg;
+        Zout[seg * NX + lane] = z;
+    }
+    WAVE_SYNC();
+    // the padding columns of Ys are operands of the product (times a zero of the Jacobian tile): zero again for the next segment
+    if (lane < NX)
+        Ys[NCOLS * NX + lane] = 0.;
+    WAVE_SYNC(); // this segment's last LDS accesses before the next segment's first
+}
+#endif // DISC_STAGE_SCHEDULE
+
+// Segments k0 .. k1-1 of instance `inst` by one wavefront.  SCHED 0 is discretizeSegment per segment, SCHED 1 one set-up and the bodies.
+template <class Model, bool FOH, bool VT, int SCHED = DISC_STAGE_SCHEDULE, bool SKIP = (RK_SKIP_DEAD != 0)>
+__device__ __forceinline__ void discretizeSegments(int B, int K, const double *__restrict__ X, const double *__restrict__ U,
+                                                   const double *__restrict__ sigma, const double *__restrict__ par, int par_stride,
+                                                   const int *__restrict__ active, double *__restrict__ Aout, double *__restrict__ Bout,
+                                                   double *__restrict__ Cout, double *__restrict__ Sout, double *__restrict__ Zout, int steps_opt,
+                                                   const long inst, const int k0, const int k1, DiscLds<Model, FOH, VT> *lds)
+{
+#if DISC_STAGE_SCHEDULE
+    if constexpr (SCHED != 0)
+    {
+        DiscTableSlots<Model> ts;
+        if (!discretizeSetup<Model, FOH, VT>(B, par, par_stride, active, inst, lds, ts))
+            return;
+        for (int k = k0; k < k1; k++)
+            discretizeSegmentBody<Model, FOH, VT, SKIP>(K, X, U, sigma, Aout, Bout, Cout, Sout, Zout, steps_opt, inst, k, lds, ts);
+    }
+    else
+#endif
+    {
+        for (int k = k0; k < k1; k++)
+        {
+            discretizeSegment<Model, FOH, VT, SKIP>(B, K, X, U, sigma, par, par_stride, active, Aout, Bout, Cout, Sout, Zout, steps_opt, inst, k, lds);
+            WAVE_SYNC(); // the segment's last LDS reads before the next segment's first writes
+        }
+    }
+}
+
+// SCHED / SKIP: what the library ships by default; <0, false> is the round-1 structure with all 13 stages (SCPP_DISC_SCHEDULE=0)
+template <class Model, bool FOH, bool VT, int SCHED = DISC_STAGE_SCHEDULE, bool SKIP = (RK_SKIP_DEAD != 0)>
 __global__ void __launch_bounds__(WAVE, DISC_WAVES_PER_SIMD)
     discretize_kernel(int B, int K, const double *__restrict__ X, const double *__restrict__ U,
                       const double *__restrict__ sigma, const double *__restrict__ par, int par_stride,
@@ -587,7 +990,7 @@ __global__ void __launch_bounds__(WAVE, DISC_WAVES_PER_SIMD)
     const long inst = (gb / nseg) * 8 + xcd;
     const int k = int(gb % nseg);
     __shared__ DiscLds<Model, FOH, VT> lds;
-    discretizeSegment<Model, FOH, VT>(B, K, X, U, sigma, par, par_stride, active, Aout, Bout, Cout, Sout, Zout, steps_opt, inst, k, &lds);
+    discretizeSegments<Model, FOH, VT, SCHED, SKIP>(B, K, X, U, sigma, par, par_stride, active, Aout, Bout, Cout, Sout, Zout, steps_opt, inst, k, k + 1, &lds);
 }
 
 // Batched nonlinear propagation  x <- x(dt)  under first-order-hold input: replaces
@@ -622,6 +1025,8 @@ __global__ void simulate_kernel(int B, const double *__restrict__ par, int par_s
 #pragma unroll
         for (int s = 0; s < RK_S; s++)
         {
+            if (RK_SKIP_DEAD && !rkStageLive(s))
+                continue; // its slope is never read (common.h)
             double ys[NX], u[NU];
             const double ts = t0 + RK_C[s] * h;
             for (int j = 0; j < NX; j++)

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <new>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -127,6 +128,7 @@ struct scpp_hip_ctx
     unsigned long long stream_ticks[4] = {0, 0, 0, 0};
     int ipm_schedule = SCPP_IPM_SCHEDULE_DEFAULT; // SCPP_IPM_RESIDENT / SCPP_IPM_SPLIT / SCPP_IPM_RESIDENT_WS (scpp_hip_set_ipm_schedule)
     int ipm_split_pairs = 0;                      // (factor, rest) launch pairs per solve of the split schedule; 0 = the worst case 2 maxit + 1
+    int disc_schedule = DISC_STAGE_SCHEDULE; // stand-alone discretize_kernel launches: 0 = the round-1 stage schedule with all 13 stages (SCPP_DISC_SCHEDULE=0, regression hook)
     int disc_steps = 5; // RKF78 steps per segment: 5 = the reference's fixed count (default since round 4), 1 .. 4 pinned, 0 = discretize_kernel.h's step-length rule (opt-in)
 };
 
@@ -290,18 +292,26 @@ int launchDiscretize(scpp_hip_ctx *c, int mode, const double *par0, int stride, 
     } v{c->X + f * K * nx, c->U + f * K * nu, c->sigma + f, c->A + f * seg * nx * nx, c->Bm + f * seg * nx * nu,
         c->C + f * seg * nx * nu, c->S + f * seg * nx, c->Z + f * seg * nx, r.stream};
     const bool timed = spanBegin(c, 0, ninst, r.stream);
-    if (mode == (SCPP_MODE_FOH | SCPP_MODE_VT))
-        hipLaunchKernelGGL((discretize_kernel<Model, true, true>), dim3(grid), dim3(WAVE), 0, v.stream, B, K, v.X, v.U,
-                           v.sigma, par, stride, active, v.A, v.Bm, v.C, v.S, v.Z, c->disc_steps);
-    else if (mode == SCPP_MODE_FOH)
-        hipLaunchKernelGGL((discretize_kernel<Model, true, false>), dim3(grid), dim3(WAVE), 0, v.stream, B, K, v.X, v.U,
-                           v.sigma, par, stride, active, v.A, v.Bm, v.C, v.S, v.Z, c->disc_steps);
-    else if (mode == SCPP_MODE_VT)
-        hipLaunchKernelGGL((discretize_kernel<Model, false, true>), dim3(grid), dim3(WAVE), 0, v.stream, B, K, v.X, v.U,
-                           v.sigma, par, stride, active, v.A, v.Bm, v.C, v.S, v.Z, c->disc_steps);
+    auto launch = [&](auto foh, auto vt, auto old) {
+        constexpr int SCHED = decltype(old)::value ? 0 : DISC_STAGE_SCHEDULE;
+        constexpr bool SKIP = decltype(old)::value ? false : (RK_SKIP_DEAD != 0);
+        hipLaunchKernelGGL((discretize_kernel<Model, decltype(foh)::value, decltype(vt)::value, SCHED, SKIP>), dim3(grid), dim3(WAVE), 0, v.stream, B, K,
+                           v.X, v.U, v.sigma, par, stride, active, v.A, v.Bm, v.C, v.S, v.Z, c->disc_steps);
+    };
+    auto launchMode = [&](auto old) {
+        if (mode == (SCPP_MODE_FOH | SCPP_MODE_VT))
+            launch(std::true_type{}, std::true_type{}, old);
+        else if (mode == SCPP_MODE_FOH)
+            launch(std::true_type{}, std::false_type{}, old);
+        else if (mode == SCPP_MODE_VT)
+            launch(std::false_type{}, std::true_type{}, old);
+        else
+            launch(std::false_type{}, std::false_type{}, old);
+    };
+    if (c->disc_schedule == 0 && (DISC_STAGE_SCHEDULE != 0 || RK_SKIP_DEAD != 0))
+        launchMode(std::true_type{});
     else
-        hipLaunchKernelGGL((discretize_kernel<Model, false, false>), dim3(grid), dim3(WAVE), 0, v.stream, B, K, v.X, v.U,
-                           v.sigma, par, stride, active, v.A, v.Bm, v.C, v.S, v.Z, c->disc_steps);
+        launchMode(std::false_type{});
     spanEnd(c, timed, r.stream);
     return hipGetLastError() == hipSuccess ? 0 : SCPP_E_HIP;
 }
@@ -634,6 +644,9 @@ int scpp_hip_create(scpp_hip_ctx **out, int device_id, int model_id, int K, int 
     if (const char *e = std::getenv("SCPP_IPM_SCHEDULE"))
         if (std::atoi(e) >= SCPP_IPM_RESIDENT && std::atoi(e) <= SCPP_IPM_SPLIT)
             c->ipm_schedule = std::atoi(e);
+    if (const char *e = std::getenv("SCPP_DISC_SCHEDULE")) // 0: this context's discretize_kernel launches in the old stage schedule (the persistent kernels have the new one only)
+        if (std::atoi(e) == 0)
+            c->disc_schedule = 0;
     if (const char *e = std::getenv("SCPP_STREAM_ENGINE"))
         if (std::atoi(e) == SCPP_STREAM_POOLS || std::atoi(e) == SCPP_STREAM_PERSISTENT)
             c->stream_engine = std::atoi(e);

@@ -238,6 +238,8 @@ __device__ __forceinline__ void scvxCostUpdate(const SCBuffers &b, const SCvxBuf
 #pragma unroll
             for (int s = 0; s < RK_S; s++)
             {
+                if (RK_SKIP_DEAD && !rkStageLive(s))
+                    continue; // its slope is never read (common.h)
                 double ys[NX], u[NU];
                 const double ts = t0 + RK_C[s] * h;
                 for (int j = 0; j < NX; j++)
@@ -342,6 +344,8 @@ __device__ __forceinline__ void scvxCostUpdateSplit(const SCBuffers &b, const SC
 #pragma unroll
             for (int s = 0; s < RK_S; s++)
             {
+                if (RK_SKIP_DEAD && !rkStageLive(s))
+                    continue; // its slope is never read (common.h); both lanes of a pair skip it, the exchange included
                 double mine[NH], ys[NX], u[NU], f[NX];
                 const double ts = t0 + RK_C[s] * h;
 #pragma unroll

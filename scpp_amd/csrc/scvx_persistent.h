@@ -160,11 +160,7 @@ PERSIST_STEP_FN void persistDiscretize(long slot)
     extern __shared__ __attribute__((aligned(16))) double seg_lds[]; // 16-byte base: DiscLds members are aligned(16) (b128 LDS accesses), whatever the static LDS before it adds up to
     DiscLds<Model, FOH, false> *lds = reinterpret_cast<DiscLds<Model, FOH, false> *>(seg_lds);
 #endif
-    for (int k = 0; k < K - 1; k++)
-    {
-        discretizeSegment<Model, FOH, false>(B, K, X, U, sigma, par, ipm::IP_N, nullptr, Ao, Bo, Co, So, Zo, steps, slot, k, lds);
-        WAVE_SYNC(); // the segment's last LDS reads before the next segment's first writes
-    }
+    discretizeSegments<Model, FOH, false>(B, K, X, U, sigma, par, ipm::IP_N, nullptr, Ao, Bo, Co, So, Zo, steps, slot, 0, K - 1, lds);
     stepFence();
 }
 template <class T, class P>
@@ -265,11 +261,7 @@ PERSIST_STEP_FN void scPersistDiscretize(long slot)
     extern __shared__ __attribute__((aligned(16))) double seg_lds[]; // 16-byte base: DiscLds members are aligned(16) (b128 LDS accesses), whatever the static LDS before it adds up to
     DiscLds<Model, FOH, VT> *lds = reinterpret_cast<DiscLds<Model, FOH, VT> *>(seg_lds);
 #endif
-    for (int k = 0; k < K - 1; k++)
-    {
-        discretizeSegment<Model, FOH, VT>(B, K, X, U, sigma, par, ipm::IP_N, nullptr, Ao, Bo, Co, So, Zo, steps, slot, k, lds);
-        WAVE_SYNC();
-    }
+    discretizeSegments<Model, FOH, VT>(B, K, X, U, sigma, par, ipm::IP_N, nullptr, Ao, Bo, Co, So, Zo, steps, slot, 0, K - 1, lds);
     stepFence();
 }
 template <class P>

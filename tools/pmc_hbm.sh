@@ -12,15 +12,19 @@ BENCH="python $ROOT/bench.py --batch $BATCH --steps $STEPS --warmup 0 --no-extra
 run_pass () { # name, counters..., -- command
   local name=$1; shift; local ctrs=(); while [ "$1" != "--" ]; do ctrs+=($1); shift; done; shift
   timeout -k 5 600 rocprofv3 --pmc "${ctrs[@]}" --output-format csv -d $OUT/$name -- "$@" > $OUT/$name.log 2>&1
-  echo "$name rc=$?"
+  local rc=$?
+  echo "$name rc=$rc"
+  return $rc
 }
-run_pass calib_fetch FETCH_SIZE -- $ROOT/tools/bin/hbm_calib
-run_pass calib_write WRITE_SIZE -- $ROOT/tools/bin/hbm_calib
-run_pass fetch FETCH_SIZE -- $BENCH
-run_pass write WRITE_SIZE -- $BENCH
-run_pass mfma SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE -- $BENCH
-run_pass tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -- $BENCH
-run_pass sq SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_VALU -- $BENCH
+# a pass that fails (a fault, an abort, the time limit) ends the session: nothing more is started on that GPU
+stop () { echo "pmc_hbm: pass failed, stopping (logs in $OUT)"; exit 1; }
+run_pass calib_fetch FETCH_SIZE -- $ROOT/tools/bin/hbm_calib || stop
+run_pass calib_write WRITE_SIZE -- $ROOT/tools/bin/hbm_calib || stop
+run_pass fetch FETCH_SIZE -- $BENCH || stop
+run_pass write WRITE_SIZE -- $BENCH || stop
+run_pass mfma SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE -- $BENCH || stop
+run_pass tcc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -- $BENCH || stop
+run_pass sq SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_VALU -- $BENCH || stop
 cd $ROOT
 for p in fetch write mfma tcc sq; do grep '^{' $OUT/$p.log | tail -1 > $OUT/$p.bench.json; done
 python - "$OUT" "$TAG" "$BATCH" "$STEPS" <<'PY'
