@@ -274,6 +274,7 @@ struct Ctx
     LDSP double *segl; // [NSEGLDS][NL][pitch] LDS-resident segment fields (main loop only)
     int K, lane;
     int pitch;   // row pitch of the field-major records (doubles)
+    int setup_v0; // != 0: the once-per-solve phases in their element-wise form (KernelArgs::setup_schedule == 0, ipm_solve.h: IPM_SETUP_SCHEDULE)
     double *st;  // [STREC][pitch]   field-major
     double *sg;  // [SEGREC][pitch]  field-major
     double *dy;  // [DYNREC][pitch]  field-major copy of A,B,C,s,z

@@ -67,6 +67,7 @@ struct KernelArgs
     int max_sc_iterations;
     int *warm;                   // [B] (may be null) 1: the workspace holds the primal-dual point of a successful previous solve
     int do_sc_update;            // 1: apply readSolution + convergence logic ; 0: plain sub-problem solve
+    int setup_schedule;          // 0: the once-per-solve phases and the solve's own copies in their element-wise form (SCPP_SETUP_SCHEDULE=0, regression hook)
     const int *dd_fresh;         // (may be null) [B] 0: A .. Z of the instance are what this workspace's PREVIOUS solve saw (SCvx: a re-solve after a rejected
                                  // candidate, SCvxAlgorithm.cpp:132-138) -- the field-major copy of dd and the data norm built on it are kept (round 6)
     double *Xold, *Uold;         // (may be null) SCvx: snapshot of the linearisation point taken before the solution
@@ -788,9 +789,209 @@ __device__ inline Views makeViews(const Ctx &c)
     return v;
 }
 
+// batched field access: all loads (stores) of a group are issued back to back; buffer stores may alias buffer
+// loads as far as the compiler knows, so every phase is written as  load group -> compute -> store group
+template <int N>
+__device__ inline void ldf(const SV &r, int f, double (&v)[N])
+{
+#pragma unroll
+    for (int i = 0; i < N; i++)
+        v[i] = r[f + i];
+}
+template <int N>
+__device__ inline void stf(const SV &r, int f, const double (&v)[N])
+{
+#pragma unroll
+    for (int i = 0; i < N; i++)
+        r[f + i] = v[i];
+}
+// the same for a row behind a plain pointer (trajectory, dynamics: row-major, one row per lane)
+template <int N>
+__device__ inline void ldp(const double *p, double (&v)[N])
+{
+#pragma unroll
+    for (int i = 0; i < N; i++)
+        v[i] = p[i];
+}
+
+// =====================================================================================================
+// The ONCE-PER-SOLVE phases (set-up, warm start, data norms) and the solve's code outside the phases follow the load-group rule of the
+// per-iteration phases since round 13 (IPM_SETUP_SCHEDULE 1).  They move little (0.4 MB against 1.9 MB of an iteration) but were written
+// element by element -- dy[e] = Ak[e], sg[f] += alpha -- and a plain-pointer load may alias the buffer store in front of it, a buffer
+// load the one before: the compiler kept the source order, load -> wait -> store, one exposed memory round trip per ELEMENT (336 for the
+// field-major copy of a RocketQuat segment alone; tools/isa_round_trips.py).  Only the order of the memory operations
+// differs: every value goes through the expressions it went through before, every sum keeps its order.
+// The element-wise functions stay (suffix V0): a context created under SCPP_SETUP_SCHEDULE=0 runs its solves through them in every kernel
+// (KernelArgs::setup_schedule -> Ctx::setup_v0), so that the two can be compared bit for bit inside one library, on the device
+// (tests/test_setup_schedule.py, tests/test_setup_schedule_gpu.py).  IPM_SETUP_SCHEDULE 0 builds a library that has the V0 path only.
+// =====================================================================================================
+#ifndef IPM_SETUP_SCHEDULE
+#define IPM_SETUP_SCHEDULE 1
+#endif
+// elements per load / store group of the field-major copy: 56 doubles = 112 VGPRs of a phase that holds little else
+#ifndef IPM_SETUP_COPY_CHUNK
+#define IPM_SETUP_COPY_CHUNK 56
+#endif
+__device__ inline bool setupV0(const PRIV Ctx *cin)
+{
+    return !IPM_SETUP_SCHEDULE || uniformInt(cin->setup_v0) != 0;
+}
+// elements [OFF, N) of one lane's row-major block -> fields f + OFF .. of its field-major record, CH at a time
+template <int N, int CH, int OFF = 0>
+__device__ __forceinline__ void copyToFields(const double *src, const SV &dst, int f)
+{
+    if constexpr (OFF < N)
+    {
+        constexpr int n = N - OFF < CH ? N - OFF : CH;
+        double r[n];
+        ldp<n>(src + OFF, r);
+        LOADS_ISSUED();
+        stf<n>(dst, f + OFF, r);
+        LOADS_ISSUED(); // (the stores stay in front of the next group's loads: in-order counter, nothing waits for them there)
+        copyToFields<N, CH, OFF + n>(src, dst, f);
+    }
+}
+
 // ---- setup: clear records, field-major copy of the dynamics, trust-region centre, fixed values ----
 template <class P>
 PHASE_FN void phSetup(const PRIV Ctx *cin, const double *Xin, const double *Uin, const double *uhatIn, PRIV Glob *gp, PRIV Iter *ip_, int warmIn, int ddSameIn)
+{
+    EMU_PHASE("phSetup");
+    using L = Lay<P>;
+    constexpr int NX = P::NX, NU = P::NU;
+    const bool warm = uniformInt(warmIn) != 0;
+    const bool dd_same = uniformInt(ddSameIn) != 0; // the workspace's field-major copy of A .. Z is still that of these data (167 KB not rewritten per re-solve)
+    const Ctx c = uniformCtx(cin);
+    const double *X = uniformPtr(Xin), *U = uniformPtr(Uin), *uhat = uniformPtr(uhatIn);
+    const Views v = makeViews<P>(c);
+    const int k = v.k, K = v.K;
+    const SV &st = v.st, &sg = v.sg, &dy = v.dy;
+    const double *ip = c.ip;
+    Glob g;
+    Iter it; // (only D and bad are written: the other fields stay where they are, in LDS, instead of in VGPRs across the copy groups)
+    g.sig = g.dsg = g.n1 = 0.;
+    g.sigbar = ip_->sigbar;
+    g.ss = g.zs = g.s3 = g.z3 = 1.;
+    for (int i = 0; i < 3; i++)
+        g.sc3[i] = g.zc3[i] = g.dsc3[i] = g.dzc3[i] = g.lamC[i] = g.dsC[i] = g.dzC[i] = 0.;
+    g.dsig = g.ddsg = g.dn1 = g.dss = g.dzs = g.ds3 = g.dz3 = 0.;
+    g.hsig = g.Hsd = g.Hdd = g.schur = 0.;
+    g.seta = 1.;
+    g.sw[0] = 1.;
+    g.sw[1] = g.sw[2] = 0.;
+    if (warm)
+    {
+        // warm start: primal point, slacks and duals of the previous solve stay in the records; the wave-uniform part
+        // was saved at the end of that solve
+        const double *gs = c.gsave;
+        g.sig = gs[0];
+        g.dsg = gs[1];
+        g.n1 = gs[2];
+        g.ss = gs[3];
+        g.zs = gs[4];
+        g.s3 = gs[5];
+        g.z3 = gs[6];
+        for (int i = 0; i < 3; i++)
+        {
+            g.sc3[i] = gs[7 + i];
+            g.zc3[i] = gs[10 + i];
+        }
+    }
+    int Dcount = 0;
+    // device memory is not zero-initialised: clear this lane's records (entries of inactive cones are
+    // never written afterwards but are swept by the vector updates)
+    if (v.vst && !warm)
+    {
+        for (int i = 0; i < L::STREC; i++)
+            st[i] = 0.;
+        for (int i = 0; i < L::XREC; i++)
+            v.xs[i] = 0.;
+    }
+    if (v.vsg && !warm)
+        for (int i = 0; i < (G_NFIELDS * L::NL); i++)
+            sg[i] = 0.;
+    const int kg = v.vsg ? k : 0, ks = v.vst ? k : 0; // (the rows of a lane without a segment / a stage are loaded from row 0 and not stored)
+    if (v.vsg && !dd_same)
+    {
+        // field-major copy of this segment's dynamics (read once row-major, re-read coalesced every iteration)
+        EMU_TRAFFIC_MANUAL("dd A, B, C, S, Z row-major (plain pointers)", NX * NX + 2 * NX * NU + 3 * NX, false);
+        copyToFields<NX * NX, IPM_SETUP_COPY_CHUNK>(c.A + size_t(k) * NX * NX, dy, L::DY_A);
+        copyToFields<NX * NU, IPM_SETUP_COPY_CHUNK>(c.B + size_t(k) * NX * NU, dy, L::DY_B);
+        copyToFields<NX * NU, IPM_SETUP_COPY_CHUNK>(c.C + size_t(k) * NX * NU, dy, L::DY_C);
+    }
+    {
+        // one group: S (the exchange record's copy and the field-major one), Z, and the trust-region centre X, U, uhat
+        double s[NX], z[NX], xb[P::NXV], ub[P::NUV], uh[3];
+        const double *Xb = X + size_t(ks) * NX, *Ub = U + size_t(ks) * NU;
+        ldp<NX>(c.S + size_t(kg) * NX, s);
+        if (!dd_same)
+            ldp<NX>(c.Z + size_t(kg) * NX, z);
+#pragma unroll
+        for (int j = 0; j < P::NXV; j++)
+            xb[j] = Xb[P::XMAP[j]];
+#pragma unroll
+        for (int j = 0; j < P::NUV; j++)
+            ub[j] = Ub[P::UMAP[j]];
+        ldp<3>(uhat + size_t(ks) * 3, uh);
+        LOADS_ISSUED();
+        if (v.vsg)
+        {
+            stf<NX>(v.xs, L::X_S, s);
+            if (!dd_same)
+            {
+                stf<NX>(dy, L::DY_S, s);
+                stf<NX>(dy, L::DY_Z, z);
+            }
+        }
+        if (v.vst)
+        {
+            EMU_TRAFFIC_MANUAL("td X, U, uhat (plain pointers)", P::NXV + P::NUV + 3, false);
+            stf<P::NXV>(st, L::F_WBAR, xb);
+            stf<P::NUV>(st, L::F_WBAR + P::NXV, ub);
+            stf<3>(st, L::F_UHAT, uh);
+        }
+    }
+    if (v.vst)
+    {
+        // presolved variables (the table's equalTo rows): x_init at the first node, x_final components / zero inputs at the last
+        // (zero-order hold: final-input equalities at node K-2, and the non-existent inputs of node K-1 pinned to 0)
+#pragma unroll
+        for (int j = 0; j < L::NVU; j++)
+        {
+            if (k == 0 && (P::FIXED_FIRST & (1u << j)))
+                st[L::F_W + j] = j < P::NXV ? ip[IP_XINIT + P::XMAP[j < P::NXV ? j : 0]] : 0.;
+            if (k == K - 1 && (L::FIX_LAST & (1u << j)))
+                st[L::F_W + j] = j < P::NXV ? ip[IP_XFINAL + P::XMAP[j < P::NXV ? j : 0]] : 0.;
+            if (k == K - 2 && (L::FIX_PRE & (1u << j)))
+                st[L::F_W + j] = 0.;
+        }
+        Dcount += __builtin_popcount(v.act);
+        // identity scalings
+        if (!warm)
+        {
+            for (int i = 0; i < L::NCONES; i++)
+                st[L::F_ETA + i] = 1.;
+#pragma unroll
+            for (int cix = 0; cix < L::NCONES; cix++)
+                st[L::F_WB + L::CONE_OFF.v[cix]] = 1.;
+        }
+    }
+    if (v.vsg)
+        Dcount += 2 * L::NL;
+    {
+        const double dsum = wave_sum(double(Dcount));
+        it.D = int(dsum + 0.5) + 3;
+    }
+    it.bad = 0;
+    storePriv(gp, g);
+    PUT_BEGIN();
+    PUT(ip_, it, D);
+    PUT(ip_, it, bad);
+    PUT_END();
+}
+// (the element-wise set-up: SCPP_SETUP_SCHEDULE=0)
+template <class P>
+PHASE_FN void phSetupV0(const PRIV Ctx *cin, const double *Xin, const double *Uin, const double *uhatIn, PRIV Glob *gp, PRIV Iter *ip_, int warmIn, int ddSameIn)
 {
     EMU_PHASE("phSetup");
     using L = Lay<P>;
@@ -1051,8 +1252,261 @@ PHASE_FN void phInitDualFinish(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip
     WAVE_SYNC();
 }
 // ---- warm start: slacks re-evaluated on the new data and pushed theta into the interior, duals likewise ----
+// evalAllSaff on register arrays: the stage's variables, centre and uhat in one load group, the slack vector in one store group; the segment rows likewise
+template <class P>
+__device__ __forceinline__ void evalAllSaffGrouped(const Ctx &c, const Glob &g, int fOut, int g1, int g2, double &os, double &o3, double *oc)
+{
+    using L = Lay<P>;
+    const int k = c.lane, K = c.K;
+    double sumnb = 0.;
+    {
+        const bool vst = k < K, vsg = k < K - 1;
+        const SV st = makeSV(c.st, L::STREC, unsigned(vst ? k : 0), c.pitch);
+        const SV sg = makeSV(c.sg, (G_NFIELDS * L::NL), unsigned(vsg ? k : 0), c.pitch);
+        const SV stz = padView(st, scvxMode(c.ip)); // SCvx: the state rows of the centre are not read (saff takes 0 for them)
+        double w[NV], wb[NV], uh[3], r[L::NS], nu[L::NL], nub[L::NL], s1[L::NL], s2[L::NL];
+        ldf<NV>(st, L::F_W, w);
+        const double dl = st[L::F_DL];
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            wb[j] = j < P::NXV ? double(stz[L::F_WBAR + j]) : (j < L::NVU ? double(st[L::F_WBAR + j]) : 0.);
+        ldf<3>(st, L::F_UHAT, uh);
+        ldf<L::NL>(sg, G_NU * L::NL, nu);
+        ldf<L::NL>(sg, G_NUB * L::NL, nub);
+        LOADS_ISSUED();
+        saff<P>(c.ip, vst ? L::activeMask(k, K) : 0u, w, dl, wb, uh, r);
+#pragma unroll
+        for (int i = 0; i < L::NL; i++)
+        {
+            s1[i] = nub[i] - nu[i];
+            s2[i] = nub[i] + nu[i];
+            if (vsg)
+                sumnb += nub[i];
+        }
+        if (vst)
+            stf<L::NS>(st, fOut, r);
+        if (vsg)
+        {
+            stf<L::NL>(sg, g1 * L::NL, s1);
+            stf<L::NL>(sg, g2 * L::NL, s2);
+        }
+    }
+    sumnb = wave_sum(sumnb);
+    os = g.sig - 0.001;
+    o3 = g.n1 - sumnb;
+    oc[0] = 0.5 + 0.5 * g.dsg;
+    oc[1] = 0.5 - 0.5 * g.dsg;
+    oc[2] = g.sig - g.sigbar;
+}
+// shiftToCone with the vector held in registers between the search for the largest violation and the shift (the element-wise form reads every
+// entry it shifts a second time, load -> wait -> store)
+template <class P>
+__device__ __forceinline__ void shiftToConeGrouped(const Ctx &c, double theta, int f, int g1, int g2, double &vs, double &v3, double *vc)
+{
+    using L = Lay<P>;
+    const int k = c.lane, K = c.K;
+    const bool vst = k < K, vsg = k < K - 1;
+    const unsigned act = vst ? L::activeMask(k, K) : 0u;
+    const SV st = makeSV(c.st, L::STREC, unsigned(vst ? k : 0), c.pitch);
+    const SV sg = makeSV(c.sg, (G_NFIELDS * L::NL), unsigned(vsg ? k : 0), c.pitch);
+    double r[L::NS], a[L::NL], b[L::NL];
+    ldf<L::NS>(st, f, r);
+    ldf<L::NL>(sg, g1 * L::NL, a);
+    ldf<L::NL>(sg, g2 * L::NL, b);
+    LOADS_ISSUED();
+    double alpha = 0.;
+#pragma unroll
+    for (int cix = 0; cix < L::NCONES; cix++)
+        if (act & (1u << cix))
+        {
+            double nrm = 0.;
+#pragma unroll
+            for (int i = 1; i < L::CONE_DIM.v[cix]; i++)
+                nrm += r[L::CONE_OFF.v[cix] + i] * r[L::CONE_OFF.v[cix] + i];
+            const double cres = r[L::CONE_OFF.v[cix]] - sqrt(nrm);
+            if (-cres > alpha)
+                alpha = -cres;
+        }
+#pragma unroll
+    for (int l = 0; l < P::NLP; l++)
+        if ((act & (1u << (L::NCONES + l))) && -r[L::LP0 + l] > alpha)
+            alpha = -r[L::LP0 + l];
+    if (vsg)
+    {
+#pragma unroll
+        for (int i = 0; i < L::NL; i++)
+        {
+            if (-a[i] > alpha)
+                alpha = -a[i];
+            if (-b[i] > alpha)
+                alpha = -b[i];
+        }
+    }
+    if (-vs > alpha)
+        alpha = -vs;
+    if (-v3 > alpha)
+        alpha = -v3;
+    {
+        const double cres = vc[0] - sqrt(vc[1] * vc[1] + vc[2] * vc[2]);
+        if (-cres > alpha)
+            alpha = -cres;
+    }
+    alpha = wave_max(alpha) + theta;
+#pragma unroll
+    for (int cix = 0; cix < L::NCONES; cix++)
+        if (act & (1u << cix))
+            st[f + L::CONE_OFF.v[cix]] = r[L::CONE_OFF.v[cix]] + alpha;
+#pragma unroll
+    for (int l = 0; l < P::NLP; l++)
+        if (act & (1u << (L::NCONES + l)))
+            st[f + L::LP0 + l] = r[L::LP0 + l] + alpha;
+    if (vsg)
+    {
+#pragma unroll
+        for (int i = 0; i < L::NL; i++)
+        {
+            a[i] += alpha;
+            b[i] += alpha;
+        }
+        stf<L::NL>(sg, g1 * L::NL, a);
+        stf<L::NL>(sg, g2 * L::NL, b);
+    }
+    vs += alpha;
+    v3 += alpha;
+    vc[0] += alpha;
+}
 template <class P>
 PHASE_FN void phWarmInit(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_)
+{
+    EMU_PHASE("phWarmInit");
+    using L = Lay<P>;
+    const Ctx c = uniformCtx(cin);
+    Glob g = loadPriv(gp);
+    const double theta = 1e-2;
+    evalAllSaffGrouped<P>(c, g, L::F_S, G_S1, G_S2, g.ss, g.s3, g.sc3);
+    WAVE_SYNC();
+    shiftToConeGrouped<P>(c, theta, L::F_S, G_S1, G_S2, g.ss, g.s3, g.sc3);
+    shiftToConeGrouped<P>(c, theta, L::F_Z, G_Z1, G_Z2, g.zs, g.z3, g.zc3);
+    storePriv(gp, g);
+    WAVE_SYNC();
+}
+// dynResF with nu = 0 and sigma = 0 (the constant part of the dynamics row), ROWS rows of A, B, C, S, Z per load group
+template <class P, int ROWS, int I0 = 0>
+__device__ __forceinline__ void dynResConstGrouped(const SV &dy, const double (&x0)[NV], const double (&w1)[NV], double *out)
+{
+    using L = Lay<P>;
+    if constexpr (I0 < P::NX)
+    {
+        constexpr int n = P::NX - I0 < ROWS ? P::NX - I0 : ROWS;
+        double a[n][P::NXV], b[n][P::NUV], cc[n][P::NUV], s[n], z[n];
+        sfor<n>([&](auto rt) {
+            SFOR_IDX(r, rt);
+            constexpr int i = I0 + r;
+            s[r] = dy[L::DY_S + i];
+            z[r] = dy[L::DY_Z + i];
+            sfor<P::NXV>([&](auto jt) {
+                SFOR_IDX(j, jt);
+                a[r][j] = dy[L::DY_A + i * P::NX + P::XMAP[j]];
+            });
+            sfor<P::NUV>([&](auto jt) {
+                SFOR_IDX(j, jt);
+                b[r][j] = dy[L::DY_B + i * P::NU + P::UMAP[j]];
+                cc[r][j] = dy[L::DY_C + i * P::NU + P::UMAP[j]];
+            });
+        });
+        LOADS_ISSUED();
+        sfor<n>([&](auto rt) {
+            SFOR_IDX(r, rt);
+            constexpr int i = I0 + r;
+            constexpr int xi = L::XINV.v[i];
+            double acc = (xi >= 0 ? double(w1[xi >= 0 ? xi : 0]) : 0.) - s[r] * 0. - 0. - z[r];
+            sfor<P::NXV>([&](auto jt) {
+                SFOR_IDX(j, jt);
+                acc -= a[r][j] * x0[j];
+            });
+            sfor<P::NUV>([&](auto jt) {
+                SFOR_IDX(j, jt);
+                acc -= b[r][j] * x0[P::NXV + j] + cc[r][j] * w1[P::NXV + j];
+            });
+            out[i] = acc;
+        });
+        LOADS_ISSUED();
+        dynResConstGrouped<P, ROWS, I0 + n>(dy, x0, w1, out);
+    }
+}
+#ifndef IPM_NORM_ROWS
+#define IPM_NORM_ROWS 2 // rows of the dynamics per load group of phDataNorms (RocketQuat: 2 x 21 doubles)
+#endif
+// ---- data norms for the termination test (ECOS-style scaling) ----
+template <class P>
+PHASE_FN void phDataNorms(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_, int ddSameIn)
+{
+    EMU_PHASE("phDataNorms");
+    using L = Lay<P>;
+    const Ctx c = uniformCtx(cin);
+    const bool dd_same = uniformInt(ddSameIn) != 0; // the norm of the dynamics' constant part is that of the previous solve of this workspace (gsave[13])
+    const Views v = makeViews<P>(c);
+    const int K = v.K;
+    const SV &st = v.st, &stN = v.stN, &dy = v.dy;
+    const double *ip = c.ip;
+    Iter it; // (reads four weights and sigbar, writes the three norms)
+    const double wtrx = ip_->wtrx, w_t = ip_->w_t, w_trt = ip_->w_trt, w_vc = ip_->w_vc, sigbar = ip_->sigbar;
+    {
+        double resx0 = sqrt(K * wtrx * wtrx + w_t * w_t + w_trt * w_trt + w_vc * w_vc);
+        resx0 = resx0 > 1. ? resx0 : 1.;
+        double nb = 0., nh = 0.;
+        double w0[NV], w1[NV], wb[NV], uh[3];
+        // one group: the pinned variables of this stage and of the next, the centre, uhat (the views of a lane without a stage read stage 0)
+        const SV stz = padView(st, scvxMode(ip)); // SCvx: the state rows of the centre are not read (saff takes 0 for them)
+        const unsigned fmn = L::fixedMask(v.k + 1, K);
+        ldf<NV>(st, L::F_W, w0);
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            wb[j] = j < P::NXV ? double(stz[L::F_WBAR + j]) : (j < L::NVU ? double(st[L::F_WBAR + j]) : 0.);
+        ldf<3>(st, L::F_UHAT, uh);
+        if (!dd_same)
+            ldf<NV>(stN, L::F_W, w1);
+        LOADS_ISSUED();
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+        {
+            w0[j] = (v.vst && (v.fm & (1u << j))) ? w0[j] : 0.;
+            w1[j] = (!dd_same && v.vsg && (fmn & (1u << j))) ? w1[j] : 0.;
+        }
+        if (v.vst)
+        {
+            double r[L::NS];
+            saff<P>(ip, v.act, w0, 0., wb, uh, r);
+            for (int i = 0; i < L::NS; i++)
+                nh += r[i] * r[i];
+        }
+        if (v.vsg && !dd_same)
+        {
+            // (loads and arithmetic in ONE block: arithmetic whose only use sits behind a later branch is sunk there, behind every group's loads)
+            double res[L::NL];
+            dynResConstGrouped<P, IPM_NORM_ROWS>(dy, w0, w1, res);
+            for (int i = 0; i < L::NL; i++)
+                nb += res[i] * res[i];
+        }
+        nb = wave_sum(nb);
+        nh = wave_sum(nh) + 0.001 * 0.001 + 0.25 + 0.25 + sigbar * sigbar;
+        it.resx0 = resx0;
+        // (same data, same pinned variables -> the same number, bit for bit: kept in the warm-start block instead of 128 KB of the copy read again)
+        it.resy0 = dd_same ? double(c.gsave[13]) : (sqrt(nb) > 1. ? sqrt(nb) : 1.);
+        if (!dd_same && c.lane == 0)
+            c.gsave[13] = it.resy0;
+        it.resz0 = sqrt(nh) > 1. ? sqrt(nh) : 1.;
+    }
+    PUT_BEGIN();
+    PUT(ip_, it, resx0);
+    PUT(ip_, it, resy0);
+    PUT(ip_, it, resz0);
+    PUT_END();
+}
+// ---- the element-wise forms (SCPP_SETUP_SCHEDULE=0) ----
+// ---- warm start: slacks re-evaluated on the new data and pushed theta into the interior, duals likewise ----
+template <class P>
+PHASE_FN void phWarmInitV0(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_)
 {
     EMU_PHASE("phWarmInit");
     using L = Lay<P>;
@@ -1068,7 +1522,7 @@ PHASE_FN void phWarmInit(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_)
 }
 // ---- data norms for the termination test (ECOS-style scaling) ----
 template <class P>
-PHASE_FN void phDataNorms(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_, int ddSameIn)
+PHASE_FN void phDataNormsV0(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_, int ddSameIn)
 {
     EMU_PHASE("phDataNorms");
     using L = Lay<P>;
@@ -1122,21 +1576,154 @@ PHASE_FN void phDataNorms(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_, in
 }
 
 
-// batched field access: all loads (stores) of a group are issued back to back; buffer stores may alias buffer
-// loads as far as the compiler knows, so every phase is written as  load group -> compute -> store group
-template <int N>
-__device__ inline void ldf(const SV &r, int f, double (&v)[N])
+// which form a context's solves take (setupV0 above)
+template <class P>
+__device__ inline void solveSetup(const PRIV Ctx *cin, const double *X, const double *U, const double *uhat, PRIV Glob *gp, PRIV Iter *ip_, int warm, int dd_same)
 {
-#pragma unroll
-    for (int i = 0; i < N; i++)
-        v[i] = r[f + i];
+    if (setupV0(cin))
+        phSetupV0<P>(cin, X, U, uhat, gp, ip_, warm, dd_same);
+#if IPM_SETUP_SCHEDULE
+    else
+        phSetup<P>(cin, X, U, uhat, gp, ip_, warm, dd_same);
+#endif
 }
-template <int N>
-__device__ inline void stf(const SV &r, int f, const double (&v)[N])
+template <class P>
+__device__ inline void solveWarmInit(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_)
 {
+    if (setupV0(cin))
+        phWarmInitV0<P>(cin, gp, ip_);
+#if IPM_SETUP_SCHEDULE
+    else
+        phWarmInit<P>(cin, gp, ip_);
+#endif
+}
+template <class P>
+__device__ inline void solveDataNorms(const PRIV Ctx *cin, PRIV Glob *gp, PRIV Iter *ip_, int dd_same)
+{
+    if (setupV0(cin))
+        phDataNormsV0<P>(cin, gp, ip_, dd_same);
+#if IPM_SETUP_SCHEDULE
+    else
+        phDataNorms<P>(cin, gp, ip_, dd_same);
+#endif
+}
+
+
+// ---- the solve's own copies, out of line like the phases (their registers are not the solve loop's) ----
+// old_td = td: the linearisation point before the solution overwrites it (SCvx)
+template <class P>
+PHASE_FN void phSnapshot(const PRIV Ctx *cin, const double *Xin, const double *Uin, double *XoldIn, double *UoldIn)
+{
+    EMU_PHASE("solve: outside the phases");
+    constexpr int NX = P::NX, NU = P::NU;
+    const int K = uniformInt(cin->K), k = threadIdx.x;
+    const double *X = uniformPtr(Xin), *U = uniformPtr(Uin);
+    double *Xold = uniformPtr(XoldIn), *Uold = uniformPtr(UoldIn);
+    if (k < K)
+    {
+        EMU_TRAFFIC_MANUAL("td X, U -> old_td snapshot (plain pointers)", NX + NU, false);
+        EMU_TRAFFIC_MANUAL("td X, U -> old_td snapshot (plain pointers)", NX + NU, true);
+        // one load group, one store group (the stores may alias the loads as far as the compiler knows: written in turns they cost a round trip per element)
+        double xr[NX], ur[NU];
+        ldp<NX>(X + size_t(k) * NX, xr);
+        ldp<NU>(U + size_t(k) * NU, ur);
+        LOADS_ISSUED();
 #pragma unroll
-    for (int i = 0; i < N; i++)
-        r[f + i] = v[i];
+        for (int j = 0; j < NX; j++)
+            Xold[size_t(k) * NX + j] = xr[j];
+#pragma unroll
+        for (int j = 0; j < NU; j++)
+            Uold[size_t(k) * NU + j] = ur[j];
+    }
+}
+template <class P>
+PHASE_FN void phSnapshotV0(const PRIV Ctx *cin, const double *Xin, const double *Uin, double *XoldIn, double *UoldIn)
+{
+    EMU_PHASE("solve: outside the phases");
+    constexpr int NX = P::NX, NU = P::NU;
+    const int K = uniformInt(cin->K), k = threadIdx.x;
+    const double *X = uniformPtr(Xin), *U = uniformPtr(Uin);
+    double *Xold = uniformPtr(XoldIn), *Uold = uniformPtr(UoldIn);
+    if (k < K)
+    {
+        EMU_TRAFFIC_MANUAL("td X, U -> old_td snapshot (plain pointers)", NX + NU, false);
+        EMU_TRAFFIC_MANUAL("td X, U -> old_td snapshot (plain pointers)", NX + NU, true);
+        for (int j = 0; j < NX; j++)
+            Xold[size_t(k) * NX + j] = X[size_t(k) * NX + j];
+        for (int j = 0; j < NU; j++)
+            Uold[size_t(k) * NU + j] = U[size_t(k) * NU + j];
+    }
+}
+// readSolution: the stage variables at record field fW -> X, U of the instance
+template <class P>
+PHASE_FN void phOutputs(const PRIV Ctx *cin, double *Xin, double *Uin, int fWin)
+{
+    EMU_PHASE("solve: outputs");
+    using L = Lay<P>;
+    constexpr int NX = P::NX, NU = P::NU;
+    const Ctx c = uniformCtx(cin);
+    const int K = c.K, k = c.lane, fW = uniformInt(fWin);
+    double *X = uniformPtr(Xin), *U = uniformPtr(Uin);
+    if (k < K)
+    {
+        EMU_TRAFFIC_MANUAL("td X, U written (plain pointers)", NX + NU, true);
+        const SV st = makeSV(c.st, L::STREC, unsigned(k), c.pitch);
+        double *Xo = X + size_t(k) * NX, *Uo = U + size_t(k) * NU;
+        // the stage's variables in one load group, then the stores (plain-pointer stores may alias the buffer loads)
+        double w[L::NVU];
+        ldf<L::NVU>(st, fW, w);
+        LOADS_ISSUED();
+        // states / inputs the table pins for the whole horizon are written as their constant (0)
+#pragma unroll
+        for (int i = 0; i < NX; i++)
+            Xo[i] = L::XINV.v[i] >= 0 ? w[L::XINV.v[i] >= 0 ? L::XINV.v[i] : 0] : 0.;
+#pragma unroll
+        for (int i = 0; i < NU; i++)
+            Uo[i] = L::UINV.v[i] >= 0 ? w[L::UINV.v[i] >= 0 ? L::UINV.v[i] : 0] : 0.;
+    }
+}
+template <class P>
+PHASE_FN void phOutputsV0(const PRIV Ctx *cin, double *Xin, double *Uin, int fWin)
+{
+    EMU_PHASE("solve: outputs");
+    using L = Lay<P>;
+    constexpr int NX = P::NX, NU = P::NU;
+    const Ctx c = uniformCtx(cin);
+    const int K = c.K, k = c.lane, fW = uniformInt(fWin);
+    double *X = uniformPtr(Xin), *U = uniformPtr(Uin);
+    if (k < K)
+    {
+        EMU_TRAFFIC_MANUAL("td X, U written (plain pointers)", NX + NU, true);
+        const SV st = makeSV(c.st, L::STREC, unsigned(k), c.pitch);
+        double *Xo = X + size_t(k) * NX, *Uo = U + size_t(k) * NU;
+        // states / inputs the table pins for the whole horizon are written as their constant (0)
+#pragma unroll
+        for (int i = 0; i < NX; i++)
+            Xo[i] = L::XINV.v[i] >= 0 ? double(st[fW + (L::XINV.v[i] >= 0 ? L::XINV.v[i] : 0)]) : 0.;
+#pragma unroll
+        for (int i = 0; i < NU; i++)
+            Uo[i] = L::UINV.v[i] >= 0 ? double(st[fW + (L::UINV.v[i] >= 0 ? L::UINV.v[i] : 0)]) : 0.;
+    }
+}
+template <class P>
+__device__ inline void solveSnapshot(const PRIV Ctx *cin, const double *X, const double *U, double *Xold, double *Uold)
+{
+    if (setupV0(cin))
+        phSnapshotV0<P>(cin, X, U, Xold, Uold);
+#if IPM_SETUP_SCHEDULE
+    else
+        phSnapshot<P>(cin, X, U, Xold, Uold);
+#endif
+}
+template <class P>
+__device__ inline void solveOutputs(const PRIV Ctx *cin, double *X, double *U, int fW)
+{
+    if (setupV0(cin))
+        phOutputsV0<P>(cin, X, U, fW);
+#if IPM_SETUP_SCHEDULE
+    else
+        phOutputs<P>(cin, X, U, fW);
+#endif
 }
 
 // =====================================================================================================
@@ -2559,6 +3146,7 @@ __device__ __forceinline__ void ipmSolveInstance(const KernelArgs &a, const int 
     c.S = a.S + size_t(inst) * (K - 1) * NX;
     c.Z = a.Z + size_t(inst) * (K - 1) * NX;
     c.ip = a.ip + size_t(inst) * IP_N;
+    c.setup_v0 = a.setup_schedule == 0;
     EMU_PHASE("solve: outside the phases");
     EMU_TRAFFIC_REGION("exchange [K][XREC]", c.sx, size_t(K) * L::XREC * 8, 8, size_t(L::XREC) * 8);
     EMU_TRAFFIC_REGION("stage [STREC][K]", c.st, size_t(c.pitch) * L::STREC * 8, size_t(c.pitch) * 8, 0);
@@ -2602,16 +3190,8 @@ __device__ __forceinline__ void ipmSolveInstance(const KernelArgs &a, const int 
     it.bk_valid = 0;
     it.bk_sig = it.bk_dsg = it.bk_n1 = it.pres_prev = 0.;
 
-    if (a.Xold && k < K)
-    {
-        EMU_TRAFFIC_MANUAL("td X, U -> old_td snapshot (plain pointers)", NX + NU, false);
-        EMU_TRAFFIC_MANUAL("td X, U -> old_td snapshot (plain pointers)", NX + NU, true);
-        const size_t o = size_t(inst) * K + k;
-        for (int j = 0; j < NX; j++)
-            a.Xold[o * NX + j] = a.X[o * NX + j];
-        for (int j = 0; j < NU; j++)
-            a.Uold[o * NU + j] = a.U[o * NU + j];
-    }
+    if (a.Xold)
+        solveSnapshot<P>(cs, a.X + size_t(inst) * K * NX, a.U + size_t(inst) * K * NU, a.Xold + size_t(inst) * K * NX, a.Uold + size_t(inst) * K * NU);
     PROF_T(tp0);
     int warm = (a.warm && a.warm[inst] != 0) ? 1 : 0;
     // a re-solve on unchanged data (only where the previous solve of this workspace ran to its end on them: it is warm-startable)
@@ -2632,11 +3212,11 @@ __device__ __forceinline__ void ipmSolveInstance(const KernelArgs &a, const int 
     for (int attempt = 0; attempt < 3; attempt++)
     {
     it.common_step = common_step;
-    phSetup<P>(cs, a.X + size_t(inst) * K * NX, a.U + size_t(inst) * K * NU, a.uhat + size_t(inst) * K * 3, gp, itp, warm, dd_same);
+    solveSetup<P>(cs, a.X + size_t(inst) * K * NX, a.U + size_t(inst) * K * NU, a.uhat + size_t(inst) * K * 3, gp, itp, warm, dd_same);
     if (warm)
     {
         // sub-problems of consecutive SC iterations are close: restart from the previous primal-dual point
-        phWarmInit<P>(cs, gp, itp);
+        solveWarmInit<P>(cs, gp, itp);
     }
     else
     {
@@ -2656,7 +3236,7 @@ __device__ __forceinline__ void ipmSolveInstance(const KernelArgs &a, const int 
         }
         phInitDualFinish<P>(cs, gp, itp);
     }
-    phDataNorms<P>(cs, gp, itp, dd_same);
+    solveDataNorms<P>(cs, gp, itp, dd_same);
     phSegLdsCopy<P, true>(cs);
     PROF_T(tp1);
     PROF_ADD(0, tp0, tp1);
@@ -2836,19 +3416,7 @@ __device__ __forceinline__ void ipmSolveInstance(const KernelArgs &a, const int 
     }
     if (status == 0)
     {
-        if (vst)
-        {
-            EMU_PHASE("solve: outputs");
-            EMU_TRAFFIC_MANUAL("td X, U written (plain pointers)", NX + NU, true);
-            double *Xo = t.X + (size_t(inst) * K + k) * NX, *Uo = t.U + (size_t(inst) * K + k) * NU;
-            // states / inputs the table pins for the whole horizon are written as their constant (0)
-#pragma unroll
-            for (int i = 0; i < NX; i++)
-                Xo[i] = L::XINV.v[i] >= 0 ? double(st[fW + (L::XINV.v[i] >= 0 ? L::XINV.v[i] : 0)]) : 0.;
-#pragma unroll
-            for (int i = 0; i < NU; i++)
-                Uo[i] = L::UINV.v[i] >= 0 ? double(st[fW + (L::UINV.v[i] >= 0 ? L::UINV.v[i] : 0)]) : 0.;
-        }
+        solveOutputs<P>(cs, t.X + size_t(inst) * K * NX, t.U + size_t(inst) * K * NU, fW);
         if (lane == 0 && c.ip[IP_SCVX] == 0. && c.ip[IP_FIXEDT] == 0.)
             t.sigma[inst] = sig; // SCvx / SC with free_final_time false: fixed final time (the sigma block is a decoupled dummy)
     }

@@ -81,6 +81,7 @@ __device__ inline Ctx splitCtx(const KernelArgs &a, int inst, int lane)
     c.Z = a.Z + size_t(inst) * (K - 1) * NX;
     c.ip = a.ip + size_t(inst) * IP_N;
     c.segl = nullptr;
+    c.setup_v0 = a.setup_schedule == 0;
     return c;
 }
 
@@ -234,10 +235,10 @@ __global__ void __launch_bounds__(WAVE, IPM_SPLIT_WAVES) __attribute__((disable_
             // (ipm_solve.h: a warm-started solve of SCAlgorithm's sub-problem takes the common step length; this schedule -- a measurement mode -- does not
             // repeat a failed cold attempt with it.  `it` lives in the resume block between launches, the flag with it)
             it.common_step = (IPM_SPLIT_STEPS && warm && c.ip[IP_SCVX] == 0.) ? 1 : 0;
-            phSetup<W>(cs, a.X + size_t(inst) * K * NX, a.U + size_t(inst) * K * NU, a.uhat + size_t(inst) * K * 3, gp, itp, warm, 0);
+            solveSetup<W>(cs, a.X + size_t(inst) * K * NX, a.U + size_t(inst) * K * NU, a.uhat + size_t(inst) * K * 3, gp, itp, warm, 0);
             if (warm)
             {
-                phWarmInit<W>(cs, gp, itp);
+                solveWarmInit<W>(cs, gp, itp);
                 pc = PC_NORMS;
             }
             else
@@ -265,7 +266,7 @@ __global__ void __launch_bounds__(WAVE, IPM_SPLIT_WAVES) __attribute__((disable_
         }
         else if (pc == PC_NORMS)
         {
-            phDataNorms<W>(cs, gp, itp, 0);
+            solveDataNorms<W>(cs, gp, itp, 0);
             status = -1;
             iter = 0;
             use_backup = false;

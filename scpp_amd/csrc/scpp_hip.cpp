@@ -129,6 +129,7 @@ struct scpp_hip_ctx
     int ipm_schedule = SCPP_IPM_SCHEDULE_DEFAULT; // SCPP_IPM_RESIDENT / SCPP_IPM_SPLIT / SCPP_IPM_RESIDENT_WS (scpp_hip_set_ipm_schedule)
     int ipm_split_pairs = 0;                      // (factor, rest) launch pairs per solve of the split schedule; 0 = the worst case 2 maxit + 1
     int disc_schedule = DISC_STAGE_SCHEDULE; // stand-alone discretize_kernel launches: 0 = the round-1 stage schedule with all 13 stages (SCPP_DISC_SCHEDULE=0, regression hook)
+    int setup_schedule = IPM_SETUP_SCHEDULE; // 0: this context's solves run the once-per-solve phases element by element, in every kernel (SCPP_SETUP_SCHEDULE=0, regression hook)
     int disc_steps = 5; // RKF78 steps per segment: 5 = the reference's fixed count (default since round 4), 1 .. 4 pinned, 0 = discretize_kernel.h's step-length rule (opt-in)
 };
 
@@ -409,6 +410,7 @@ ipm::KernelArgs ipmArgs(scpp_hip_ctx *c, int do_sc_update, bool masked, Range r,
     a.max_sc_iterations = c->sc.max_iterations;
     a.warm = c->ipm_warm + f;
     a.do_sc_update = do_sc_update;
+    a.setup_schedule = c->setup_schedule;
     a.dd_fresh = (snapshot && c->ipm_schedule == SCPP_IPM_RESIDENT) ? c->vx_needs_disc + f : nullptr; // SCvx rounds: needs_disc == 0 <=> a re-solve on the old dd
     a.Xold = snapshot ? c->vx_Xold + f * K * nx : nullptr;
     a.Uold = snapshot ? c->vx_Uold + f * K * nu : nullptr;
@@ -647,6 +649,9 @@ int scpp_hip_create(scpp_hip_ctx **out, int device_id, int model_id, int K, int 
     if (const char *e = std::getenv("SCPP_DISC_SCHEDULE")) // 0: this context's discretize_kernel launches in the old stage schedule (the persistent kernels have the new one only)
         if (std::atoi(e) == 0)
             c->disc_schedule = 0;
+    if (const char *e = std::getenv("SCPP_SETUP_SCHEDULE")) // 0: this context's solves take the element-wise set-up, warm start, data norms and copies (ipm_solve.h: IPM_SETUP_SCHEDULE)
+        if (std::atoi(e) == 0)
+            c->setup_schedule = 0;
     if (const char *e = std::getenv("SCPP_STREAM_ENGINE"))
         if (std::atoi(e) == SCPP_STREAM_POOLS || std::atoi(e) == SCPP_STREAM_PERSISTENT)
             c->stream_engine = std::atoi(e);

@@ -61,6 +61,7 @@ __device__ inline Ctx uniformCtx(const LDSP Ctx *cin)
     c.K = uniformInt(cin->K);
     c.lane = threadIdx.x;
     c.pitch = uniformInt(cin->pitch);
+    c.setup_v0 = uniformInt(cin->setup_v0);
     c.st = uniformPtr(cin->st);
     c.sg = uniformPtr(cin->sg);
     c.dy = uniformPtr(cin->dy);
