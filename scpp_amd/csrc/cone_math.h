@@ -80,7 +80,7 @@ __device__ inline void conicProduct(int d, AU u, AV v, AO out)
     for (int i = 0; i < d; i++)
         s0 += u[i] * v[i];
     for (int i = 1; i < d; i++)
-        out[i] = u[0] * v[i] + v[0] * u[i];
+        out[i] = u[0] * v[i] + v[0] * u[i] + 0.; // (+ 0.: a row that is zero in u and v gives +0., not -0. for u0, v0 < 0; no other bit changes)
     out[0] = s0;
 }
 // solve lam o out = dd  (out may alias dd)
@@ -202,7 +202,7 @@ __device__ inline void conicProductS(const double (&u)[D], const double (&v)[D],
         s0 += u[i] * v[i];
 #pragma unroll
     for (int i = 1; i < D; i++)
-        out[i] = u[0] * v[i] + v[0] * u[i];
+        out[i] = u[0] * v[i] + v[0] * u[i] + 0.; // (+ 0.: a row that is zero in u and v gives +0., not -0. for u0, v0 < 0; no other bit changes)
     out[0] = s0;
 }
 template <int D>
