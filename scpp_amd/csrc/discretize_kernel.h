@@ -77,6 +77,28 @@ constexpr int DISC_STEPS_MAX = 5;
 #undef DISC_STAGE_SCHEDULE
 #define DISC_STAGE_SCHEDULE 0
 #endif
+// LDS reads of schedule 1 in groups.  The compiler pairs the table passes' factor reads with their products (two ds_read_b64, wait, multiply, two
+// more, wait ...: eight serial LDS round trips for the 16 factors of pass 0) and lets the operand reads trickle in between the MFMAs: 18 exposed
+// LDS round trips per stage where the data flow needs three (stage value and hoists -> pass 0 -> pass 1 -> operands).  1: every barrier interval
+// of a stage requests all it reads first, a scheduling barrier closes the group (what LOADS_ISSUED() does for the solver's vector-memory loads),
+// then the arithmetic runs as written; what a stage needs of the read-only input table uh is requested one stage ahead, with the operand group.
+// Only the order of LDS operations changes: no expression, operand order or contraction.  0: the statement order of before.
+#ifndef DISC_LDS_GROUPS
+#define DISC_LDS_GROUPS 1
+#endif
+#if defined(SCPP_HIP_EMU) || !DISC_LDS_GROUPS
+#define DISC_READS_ISSUED()
+#else
+#define DISC_READS_ISSUED() __builtin_amdgcn_sched_barrier(0)
+#endif
+// the live stage after s (RK_S: none), with or without the dead stage
+constexpr int rkNextStage(int s, bool skip)
+{
+    for (int r = s + 1; r < RK_S; r++)
+        if (!skip || rkStageLive(r))
+            return r;
+    return RK_S;
+}
 
 template <class Model, bool FOH, bool VT>
 struct DiscLayout
@@ -703,6 +725,11 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
         nsteps = nsteps < 1 ? 1 : (nsteps > DISC_STEPS_MAX ? DISC_STEPS_MAX : nsteps);
     }
     nsteps = uniformInt(nsteps);
+    const int row = lane & 15, g = lane >> 4;
+    const bool lane_on = row < NX;
+#ifndef SCPP_HIP_EMU
+    __builtin_assume(g >= 0 && g < NG);
+#endif
     double u0[NU], u1[NU];
 #pragma unroll
     for (int i = 0; i < NU; i++)
@@ -710,6 +737,10 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
         u0[i] = U[(inst * K + k) * NU + i];
         u1[i] = FOH ? U[(inst * K + k + 1) * NU + i] : u0[i];
     }
+#if DISC_LDS_GROUPS
+    const double x0r = lane_on ? X[(inst * K + k) * NX + row] : 0.; // the segment's global loads in one group
+    DISC_READS_ISSUED();
+#endif
     if (lane == 0)
     {
 #pragma unroll
@@ -746,12 +777,9 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
     }
     WAVE_SYNC();
 
-    const int row = lane & 15, g = lane >> 4;
-    const bool lane_on = row < NX;
-#ifndef SCPP_HIP_EMU
-    __builtin_assume(g >= 0 && g < NG);
-#endif
+#if !DISC_LDS_GROUPS
     const double x0r = lane_on ? X[(inst * K + k) * NX + row] : 0.;
+#endif
     double y[EPL];
     bool eon[EPL];
 #pragma unroll
@@ -769,6 +797,15 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
 
     double kk[RK_S][EPL];
     const double h = dt / double(nsteps);
+#if DISC_LDS_GROUPS
+    // what a stage takes from the input table uh (written once per segment, read-only from here on): t / dt, and the entry lanes < NU + NUAUX copy
+    // into W_U / W_UAUX.  Requested one stage ahead, with the operand group of the stage before; the first stage's here.
+    const bool ucp = lane < NU + NUAUX;
+    const int usrc = lane < NU ? NUAUX + 1 + lane : (ucp ? lane - NU : 0);
+    const int udst = lane < NU ? TB::W_U + lane : TB::W_UAUX + lane - NU;
+    double uop_n = uh[usrc];
+    double frac_n = FOH ? uh[NUAUX] : 0.;
+#endif
     for (int step = 0; step < nsteps; step++)
     {
         forEachStage([&](auto sc) {
@@ -812,18 +849,42 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
                     for (int i = 0; i < TB::NH; i++)
                         Wt[TB::W_H + i] = hh[i];
                 }
+#if DISC_LDS_GROUPS
+                if (ucp)
+                    Wt[udst] = uop_n;
+#else
                 if (lane < NU)
                     Wt[TB::W_U + lane] = uh[e * UHP + NUAUX + 1 + lane];
                 else if (lane < NU + NUAUX)
                     Wt[TB::W_UAUX + lane - NU] = uh[e * UHP + lane - NU];
+#endif
             }
             WAVE_SYNC();
+#if DISC_LDS_GROUPS
+            const double frac = frac_n;
+#else
             const double frac = FOH ? uh[e * UHP + NUAUX] : 0.; // t / dt, tabulated with the input
+#endif
             const char *wb = reinterpret_cast<const char *>(Wt);
 #pragma unroll
             for (int ps = 0; ps < 2; ps++)
             {
                 double val = 0.;
+#if DISC_LDS_GROUPS
+                double fc[TB::MAXMON][4]; // every factor of the pass, then the products
+#pragma unroll
+                for (int q = 0; q < (ps == 0 ? TB::MAXMON : TB::MAXMON_B); q++)
+                {
+                    fc[q][0] = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][0] & 0xFFFFu));
+                    fc[q][1] = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][0] >> 16));
+                    fc[q][2] = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][1] & 0xFFFFu));
+                    fc[q][3] = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][1] >> 16));
+                }
+                DISC_READS_ISSUED();
+#pragma unroll
+                for (int q = 0; q < (ps == 0 ? TB::MAXMON : TB::MAXMON_B); q++)
+                    val += ((ts.tcf[ps][q] * fc[q][0]) * fc[q][1]) * (fc[q][2] * fc[q][3]);
+#else
 #pragma unroll
                 for (int q = 0; q < (ps == 0 ? TB::MAXMON : TB::MAXMON_B); q++)
                 {
@@ -833,6 +894,7 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
                     const double f3 = *reinterpret_cast<const double *>(wb + (ts.tof[ps][q][1] >> 16));
                     val += ((ts.tcf[ps][q] * f0) * f1) * (f2 * f3);
                 }
+#endif
                 if (ts.ttg[ps] >= 0)
                     Wt[ts.ttg[ps]] = val;
                 WAVE_SYNC();
@@ -843,9 +905,51 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
             for (int t = 0; t < 4; t++)
             {
                 const double v = Wt[TB::W_J + rowc * NJ + (4 * t + g < NX ? 4 * t + g : 0)];
+#if DISC_LDS_GROUPS
+                bsel[t] = v; // (the selection: behind the group)
+#else
                 bsel[t] = (4 * t + g < NX) ? v : 0.; // columns >= NX belong to the inputs
+#endif
             }
             const double fr = Wt[TB::W_F + rowc]; // f[row] (unscaled)
+#if DISC_LDS_GROUPS
+            // which forcing column of the Jacobian tile slot m takes: J[row, NX + jj], jj is lane dependent (-1: the slot has no B or C column)
+            auto forcingCol = [&](int m) {
+                const int c = m * NG + g;
+                const bool slotB = m * NG < L::COL_B + NU && m * NG + NG > L::COL_B;
+                const bool slotC = FOH && m * NG < L::COL_C + NU && m * NG + NG > L::COL_C;
+                if (!(slotB || slotC))
+                    return -1;
+                const bool isB = c >= L::COL_B && c < L::COL_B + NU;
+                const bool isC = FOH && c >= L::COL_C && c < L::COL_C + NU;
+                return isB ? c - L::COL_B : isC ? c - L::COL_C : 0;
+            };
+            // the rest of the operand group: the forcing entries, the A operands of the two MFMA chains, and the next stage's share of uh
+            double jbv[EPL], ya0[4], ya1[4];
+#pragma unroll
+            for (int m = 0; m < EPL; m++)
+            {
+                const int jj = forcingCol(m);
+                jbv[m] = jj >= 0 ? Wt[TB::W_J + rowc * NJ + NX + jj] : 0.;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                ya0[t] = Yb[row * NX + g + 4 * t];
+                ya1[t] = NCOLS > 16 ? Yb[(16 + row) * NX + g + 4 * t] : 0.;
+            }
+            {
+                constexpr int sn = rkNextStage(s, SKIP);
+                // (after the last stage of the last step: the first entry again, never used)
+                const int en = sn < RK_S ? step * RK_S + sn : (step + 1 < nsteps ? (step + 1) * RK_S : 0);
+                uop_n = uh[en * UHP + usrc];
+                frac_n = FOH ? uh[en * UHP + NUAUX] : 0.;
+            }
+            DISC_READS_ISSUED();
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                bsel[t] = (4 * t + g < NX) ? bsel[t] : 0.; // columns >= NX belong to the inputs
+#endif
             // ---- derivative of the owned entries: d(row, c) = J[row,:] V[:,c] + forcing(row, c), branch-free ----
             const double alphaB = FOH ? (1. - frac) : 1.;
             d4_t acc0 = {0., 0., 0., 0.}, acc1 = {0., 0., 0., 0.};
@@ -854,9 +958,16 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
             {
                 const int kx = g + 4 * t; // contraction index = state j
                 const double b = bsel[t] * tscale; // sigma scaling of A applied to the four entries this lane contributes
+#if DISC_LDS_GROUPS
+                (void)kx;
+                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ya0[t], b, acc0, 0, 0, 0);
+                if (NCOLS > 16)
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ya1[t], b, acc1, 0, 0, 0);
+#else
                 acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Yb[row * NX + kx], b, acc0, 0, 0, 0);
                 if (NCOLS > 16)
                     acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Yb[(16 + row) * NX + kx], b, acc1, 0, 0, 0);
+#endif
             }
 #pragma unroll
             for (int m = 0; m < EPL; m++)
@@ -873,7 +984,12 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
                     const bool isC = FOH && c >= L::COL_C && c < L::COL_C + NU;
                     const int jj = isB ? c - L::COL_B : isC ? c - L::COL_C : 0;
                     const double w = isB ? alphaB : isC ? frac : 0.;
+#if DISC_LDS_GROUPS
+                    (void)jj;
+                    const double jb = jbv[m];
+#else
                     const double jb = Wt[TB::W_J + rowc * NJ + NX + jj]; // J[row, NX + jj], jj is lane dependent
+#endif
                     d += (w * tscale) * jb;                              // sigma scaling of B
                 }
                 if (VT && m * NG <= L::COL_S && m * NG + NG > L::COL_S)
@@ -922,6 +1038,37 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
     WAVE_SYNC();
     if (lane < NX)
     {
+#if DISC_LDS_GROUPS
+        // the columns of the identity as one group, then the chain in the same order
+        double za[NX], zx[NX], zb[NU], zc[NU];
+        double z = Ys[lane]; // x(dt)
+#pragma unroll
+        for (int j = 0; j < NX; j++)
+        {
+            za[j] = Ys[(L::COL_PHI + j) * NX + lane];
+            zx[j] = Ys[NCOLS * NX + j];
+        }
+#pragma unroll
+        for (int j = 0; j < NU; j++)
+        {
+            zb[j] = Ys[(L::COL_B + j) * NX + lane];
+            zc[j] = FOH ? Ys[(L::COL_C + j) * NX + lane] : 0.;
+        }
+        const double zs = VT ? Ys[L::COL_S * NX + lane] : 0.;
+        DISC_READS_ISSUED();
+#pragma unroll
+        for (int j = 0; j < NX; j++)
+            z -= za[j] * zx[j];
+#pragma unroll
+        for (int j = 0; j < NU; j++)
+        {
+            z -= zb[j] * u0[j];
+            if (FOH)
+                z -= zc[j] * u1[j];
+        }
+        if (VT)
+            z -= zs * sg;
+#else
         double z = Ys[lane]; // x(dt)
 #pragma unroll
         for (int j = 0; j < NX; j++)
@@ -935,6 +1082,7 @@ __device__ __forceinline__ void discretizeSegmentBody(int K, const double *__res
         }
         if (VT)
             z -= Ys[L::COL_S * NX + lane] * sg;
+#endif
         Zout[seg * NX + lane] = z;
     }
     WAVE_SYNC();
