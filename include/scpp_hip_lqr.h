@@ -19,6 +19,7 @@
  *       (the differential Riccati equation along the trajectory)               scpp_hip_lqr_compute_gains_riccati, _download_riccati
  *   nothing: the reference has no covariance analysis                                         scpp_hip_lqr_set_covariance_inputs,
  *       (the closed-loop Lyapunov equation along the trajectory)               scpp_hip_lqr_propagate_covariance, _download_covariance
+ *       (the covariance recursion of the loop that holds its correction)       scpp_hip_lqr_propagate_covariance_discrete
  *   nothing: the reference has no sampled-data controller                                     scpp_hip_lqr_compute_gains_discrete, _download_discrete,
  *       (the discrete Riccati recursion over the segments' transition matrices) scpp_hip_lqr_set_feedback_hold
  *
@@ -61,8 +62,26 @@
  *         S_i = R dt + Gamma_i'P_{i+1} Gamma_i,   N_i = Gamma_i'P_{i+1} Phi_i,   L_i L_i' = S_i (Cholesky, lower),   Y_i = L_i^-1 N_i,
  *         K_i = L_i^-T Y_i,                       P_i = Q dt + Phi_i'P_{i+1} Phi_i - Y_i'Y_i.
  *     Node K-1 has no segment behind it: its gain is a copy of K_{K-2} and its P is Qf.  P is symmetric TO THE BIT at every node: Y'Y is by
- *     construction, and Phi'(P Phi) is symmetrised once per node, (F + F') / 2.  The covariance sweep does NOT know this law's hold: it describes
- *     the continuous loop u = u_ref - K_t (x - x_ref), whatever gains it is given.
+ *     construction, and Phi'(P Phi) is symmetrised once per node, (F + F') / 2.  scpp_hip_lqr_propagate_covariance does NOT know this law's
+ *     hold: it describes the continuous loop u = u_ref - K_t (x - x_ref), whatever gains it is given.  The covariance of the held loop is
+ *     scpp_hip_lqr_propagate_covariance_discrete:
+ *   - scpp_hip_lqr_propagate_covariance_discrete is an addition: linear covariance analysis of the loop du_i = -G[i] dx(t_i), held over
+ *     segment i (the loop of scpp_hip_lqr_set_feedback_hold(1)).  Taken unchanged from the discrete gain sweep: the reference inside segment i,
+ *     x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]), j = i+1 (first-order hold) or i (zero-order hold); the segment index, the
+ *     loop's and never recomputed from a time; RKF78 with the plant step's tableau and 8th-order weights, steps >= 1 steps per segment, stage
+ *     s of step n at a = (n + c_s) / steps; A and B, the generated Jacobian rows on the full state of every model (RocketQuat: 14 states).
+ *     G is whatever gains the context holds: discrete, Riccati, frozen or scpp_hip_lqr_set_gains.  A disturbance of constant intensity
+ *     W = diag(w) acts during the segment:
+ *         d[Phi | Gamma]/dt = A(t) [Phi | Gamma] + [0 | B(t)],   [Phi | Gamma](t_i) = [I | 0]     (the discrete gain sweep's own equation)
+ *         dM/dt = A(t) M + M A(t)' + W,   M(t_i) = 0,   Wd_i = M(t_{i+1})     (what the segment accumulates; A is the open-loop Jacobian,
+ *                                                                              because the held input does not react inside a segment)
+ *         Acl_i = Phi_i - Gamma_i G[i],   S_{i+1} = Acl_i S_i Acl_i' + Wd_i,   S_0 = sigma0.
+ *     Node k records S_k, sqrt(diag S_k) and the input covariance G[k] S_k G[k]': for k <= K-2 the covariance of the correction actually held
+ *     over segment k; node K-1 reports it with the node's own gain, for uniformity with the continuous sweep.  Node 0 records sigma0 exactly.
+ *     S is symmetric TO THE BIT at every node: M is by construction (A M and M A' are both formed, from the same products in the same
+ *     order), Acl (S Acl') is symmetrised once per node, (F + F') / 2, as the discrete gain sweep treats Phi'(P Phi), and sigma0 has to be
+ *     symmetric to the bit, as for the continuous sweep.  With w NULL or all zero the M integration is skipped as a whole; the result is
+ *     bitwise that of Wd = 0.
  *
  *   - input limits (scpp_hip_lqr_set_input_limits) are an addition to the tracking loop, off by default: with limits (T_min, T_max, angle_max)
  *     the loop applies u = sat(u_cmd), u_cmd = -K_t (x - x_ref) + u_ref computed as without them.  A non-finite u_cmd retires the flight with
@@ -152,8 +171,9 @@ extern "C"
        mode 1: held over a segment: du = -G[i] (x - x_ref(t)) is latched at the first plant step whose segment index i differs from the
        latched one (flight start counts as such a step), and u_cmd = u_ref(t) + du on every plant step, u_ref interpolated as in mode 0.
        max_dev, the non-finite retirement, input limits (the clip acts on u_cmd), the record, sample fans and the stop tolerance work as in
-       mode 0.  Anything else: SCPP_E_ARG.  The mode stays until it is set again; it invalidates neither gains nor a covariance sweep (which
-       describes the continuous loop of mode 0). */
+       mode 0.  Anything else: SCPP_E_ARG.  The mode stays until it is set again; it invalidates neither gains nor a covariance sweep (each
+       sweep describes one loop whatever the mode: scpp_hip_lqr_propagate_covariance the continuous loop of mode 0,
+       scpp_hip_lqr_propagate_covariance_discrete the held loop of mode 1). */
     int scpp_hip_lqr_set_feedback_hold(scpp_hip_lqr_ctx *ctx, int mode);
     /* gains [B][K][nu][nx], status [B][K] int32, iters [B][K] int32 (sign iterations, or RKF78 steps behind the node); any pointer may be NULL */
     int scpp_hip_lqr_download_gains(scpp_hip_lqr_ctx *ctx, double *gains, int *status, int *iters);
@@ -173,6 +193,13 @@ extern "C"
        neither the gains nor the tracking state; computing or setting gains, new trajectories, flow parameters or covariance inputs
        invalidate it. */
     int scpp_hip_lqr_propagate_covariance(scpp_hip_lqr_ctx *ctx, int steps, int keep_cov, int *n_ok);
+    /* the same for the loop that holds its correction over a segment (the definition is above): one forward sweep of
+       S_{i+1} = Acl_i S_i Acl_i' + Wd_i per trajectory under the gains the context holds, steps >= 1 RKF78 steps per segment for
+       [Phi | Gamma] and for Wd.  Preconditions, SCPP_E_* answers, inputs (scpp_hip_lqr_set_covariance_inputs), per-trajectory status and what
+       invalidates the sweep are those of scpp_hip_lqr_propagate_covariance; a Phi, Gamma, Wd, S or input covariance that turns non-finite in
+       segment k zeroes node k+1, every later node and final_cov.  The result lands where scpp_hip_lqr_download_covariance reads it, which
+       returns the last sweep of either kind.  Neither sweep changes gains, tracking state or the feedback-hold mode. */
+    int scpp_hip_lqr_propagate_covariance_discrete(scpp_hip_lqr_ctx *ctx, int steps, int keep_cov, int *n_ok);
     /* state_std [B][K][nx] = sqrt of the diagonal of S(t_k) (an entry negative from rounding counts as 0), input_cov [B][K][nu][nu] =
        G[k] S(t_k) G[k]' (symmetric to rounding), final_cov [B][nx][nx] = S(T), status [B] int32, cov [B][K][nx][nx] = S(t_k); any pointer may
        be NULL.  SCPP_E_STATE before a sweep, and for cov after a sweep with keep_cov == 0. */

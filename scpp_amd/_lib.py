@@ -486,6 +486,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_set_covariance_inputs", "scpp_hip_lqr_propagate_covariance", "scpp_hip_lqr_download_covariance",
     "scpp_hip_lqr_set_input_limits", "scpp_hip_lqr_track_samples", "scpp_hip_lqr_track_download_saturation",
     "scpp_hip_lqr_compute_gains_discrete", "scpp_hip_lqr_download_discrete", "scpp_hip_lqr_set_feedback_hold",
+    "scpp_hip_lqr_propagate_covariance_discrete",
 ]
 _lqr_libs = {}
 
@@ -615,6 +616,14 @@ class LqrContext:
         """one closed-loop covariance sweep per trajectory under the gains held; returns the number of trajectories with status 0"""
         n = C.c_int()
         _chk(self.lib.scpp_hip_lqr_propagate_covariance(self.h, int(steps), int(bool(keep_cov)), C.byref(n)), "lqr_propagate_covariance")
+        return int(n.value)
+
+    def propagate_covariance_discrete(self, steps=5, keep_cov=False):
+        """the same for the loop that holds its correction over a segment (du_i = -G[i] dx(t_i)): S_{i+1} = Acl_i S_i Acl_i' + Wd_i; the result
+        lands where download_covariance reads it"""
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_propagate_covariance_discrete(self.h, int(steps), int(bool(keep_cov)), C.byref(n)),
+             "lqr_propagate_covariance_discrete")
         return int(n.value)
 
     def download_covariance(self, with_cov=False):

@@ -5,6 +5,7 @@
 #include "lqr_riccati_kernel.h"
 #include "lqr_covariance_kernel.h"
 #include "lqr_discrete_kernel.h"
+#include "lqr_covariance_discrete_kernel.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -205,6 +206,42 @@ static int growFlights(scpp_hip_lqr_ctx *c, size_t F)
         return SCPP_E_HIP;
     c->fl_cap = F;
     return SCPP_OK;
+}
+
+// one covariance sweep per trajectory: the continuous loop's (lqr_covariance_kernel) or, with `discrete`, the node-rate hold's
+// (lqr_covariance_discrete_kernel); both take the same inputs and leave their result in the same buffers
+static int propagateCovariance(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok, bool discrete)
+{
+    if (!c || steps < 1)
+        return SCPP_E_ARG;
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B))
+        return SCPP_E_STATE; // no gains, no initial covariance, or one for another number of trajectories
+    DeviceGuard guard(c->device);
+    const size_t need = size_t(c->B) * c->K * c->nx * c->nx;
+    c->have_cov = false;
+    if (keep_cov)
+        if (int rc = growTo(c, &c->cov, &c->cov_cap, need))
+            return rc;
+    int rc = launchKernel(c, [&](auto pl) {
+        using P = decltype(pl);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
+                               (const double *)c->par, c->par_stride, (const double *)c->G, (const int *)(c->gains_computed ? c->gstatus : nullptr),
+                               (const double *)c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, (const double *)c->cw, c->cstd, c->cin, c->cfin, c->cstatus,
+                               keep_cov ? c->cov : (double *)nullptr);
+        };
+        if (discrete)
+            go(lqr_covariance_discrete_kernel<P>);
+        else
+            go(lqr_covariance_kernel<P>);
+    });
+    if (rc)
+        return rc;
+    c->have_cov = true;
+    c->cov_kept = keep_cov != 0;
+    return countOk(c, c->cstatus, size_t(c->B), n_ok);
 }
 
 extern "C"
@@ -619,30 +656,12 @@ int scpp_hip_lqr_set_covariance_inputs(scpp_hip_lqr_ctx *c, const double *sigma0
 
 int scpp_hip_lqr_propagate_covariance(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok)
 {
-    if (!c || steps < 1)
-        return SCPP_E_ARG;
-    if (int rc = readyToLaunch(c))
-        return rc;
-    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B))
-        return SCPP_E_STATE; // no gains, no initial covariance, or one for another number of trajectories
-    DeviceGuard guard(c->device);
-    const size_t need = size_t(c->B) * c->K * c->nx * c->nx;
-    c->have_cov = false;
-    if (keep_cov)
-        if (int rc = growTo(c, &c->cov, &c->cov_cap, need))
-            return rc;
-    int rc = launchKernel(c, [&](auto pl) {
-        using P = decltype(pl);
-        hipLaunchKernelGGL((lqr_covariance_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
-                           (const double *)c->par, c->par_stride, (const double *)c->G, (const int *)(c->gains_computed ? c->gstatus : nullptr),
-                           (const double *)c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, (const double *)c->cw, c->cstd, c->cin, c->cfin, c->cstatus,
-                           keep_cov ? c->cov : (double *)nullptr);
-    });
-    if (rc)
-        return rc;
-    c->have_cov = true;
-    c->cov_kept = keep_cov != 0;
-    return countOk(c, c->cstatus, size_t(c->B), n_ok);
+    return propagateCovariance(c, steps, keep_cov, n_ok, false);
+}
+
+int scpp_hip_lqr_propagate_covariance_discrete(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok)
+{
+    return propagateCovariance(c, steps, keep_cov, n_ok, true);
 }
 
 int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *c, double *state_std, double *input_cov, double *final_cov, int *status, double *cov)

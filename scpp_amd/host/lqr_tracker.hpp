@@ -51,12 +51,15 @@ struct lqr_gain_options_t
 // the closed-loop covariance sweep (scpp_hip_lqr_propagate_covariance): dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0, under the gains the tracker
 // holds.  sigma0: one symmetric [NX][NX] matrix for every trajectory or [B][NX][NX], row-major; disturbance: the diagonal of W, empty: W = 0;
 // steps: RKF78 steps per segment; keep: S(t_k) of every node is downloaded into lqr_covariance_result_t::cov.
+// hold_node: the sweep of the loop that holds its correction over a segment instead (scpp_hip_lqr_propagate_covariance_discrete; the loop
+// setFeedbackHold(true) flies): S_{i+1} = Acl_i S_i Acl_i' + Wd_i, Acl_i = Phi_i - Gamma_i G[i].
 struct lqr_covariance_options_t
 {
     std::vector<double> sigma0;
     std::vector<double> disturbance;
     int steps = 5;
     bool keep = false;
+    bool hold_node = false;
 };
 
 struct lqr_covariance_result_t
@@ -318,7 +321,10 @@ public:
         check(scpp_hip_lqr_set_covariance_inputs(ctx, o.sigma0.data(), int(o.sigma0.size() / (NX * NX)),
                                                  o.disturbance.empty() ? nullptr : o.disturbance.data()),
               "scpp_hip_lqr_set_covariance_inputs");
-        check(scpp_hip_lqr_propagate_covariance(ctx, o.steps, o.keep ? 1 : 0, &out.n_ok), "scpp_hip_lqr_propagate_covariance");
+        if (o.hold_node)
+            check(scpp_hip_lqr_propagate_covariance_discrete(ctx, o.steps, o.keep ? 1 : 0, &out.n_ok), "scpp_hip_lqr_propagate_covariance_discrete");
+        else
+            check(scpp_hip_lqr_propagate_covariance(ctx, o.steps, o.keep ? 1 : 0, &out.n_ok), "scpp_hip_lqr_propagate_covariance");
         out.state_std.assign(B * K * NX, 0.);
         out.input_cov.assign(B * K * NU * NU, 0.);
         out.final_cov.assign(B * NX * NX, 0.);

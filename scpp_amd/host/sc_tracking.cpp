@@ -13,6 +13,9 @@
 //                         S(0) = diag(initial_std)^2 and W = diag(disturbance_std)^2 from the optional vectors initial_std / disturbance_std of
 //                         LQR.info (absent: 0); --covariance-steps n RKF78 steps per segment (5).  Writes state_std.txt (one node per row) and
 //                         input_cov.txt (one node per row, the nu x nu matrix row-major) of instance 0 next to X.txt
+//   --covariance-hold step|node : which loop --covariance describes.  step (default): the continuous loop; node: the loop that latches its
+//                         correction at each node and holds it over the segment (scpp_hip_lqr_propagate_covariance_discrete), the loop
+//                         --hold node flies.  Used only with --covariance; the same two files
 //   --saturate          : input limits inside the closed loop (scpp_hip_lqr_set_input_limits), from the model's parameters T_min, T_max,
 //                         gimbal_max.  Writes n_sat.txt (plant steps on which the input was clipped) and max_clip.txt (largest |u_cmd - u|),
 //                         one flight per row, next to X.txt
@@ -43,7 +46,7 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
-    bool covariance = false, saturate = false, hold_node = false;
+    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false;
     int covariance_steps = 5, samples = 1;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
@@ -100,6 +103,16 @@ int main(int argc, char **argv)
             covariance = true;
         else if (!std::strcmp(argv[i], "--covariance-steps"))
             covariance_steps = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--covariance-hold"))
+        {
+            const std::string which = next();
+            if (which != "step" && which != "node")
+            {
+                std::fprintf(stderr, "--covariance-hold %s: step or node\n", which.c_str());
+                return 2;
+            }
+            covariance_hold_node = which == "node";
+        }
         else if (!std::strcmp(argv[i], "--saturate"))
             saturate = true;
         else if (!std::strcmp(argv[i], "--samples"))
@@ -168,6 +181,7 @@ int main(int argc, char **argv)
             constexpr size_t NX = Model::state_dim;
             scpp::lqr_covariance_options_t co;
             co.steps = covariance_steps;
+            co.hold_node = covariance_hold_node;
             const std::vector<double> sd0 = scpp::LQRTracker::loadOptionalVector("initial_std");
             co.disturbance = scpp::LQRTracker::loadOptionalVector("disturbance_std");
             co.sigma0.assign(NX * NX, 0.);
@@ -181,6 +195,8 @@ int main(int argc, char **argv)
             const size_t rhs = N * (r.td[0].n_X() - 1) * size_t(covariance_steps) * 13;
             std::printf("Covariance: %d RKF78 steps per segment, %zu right-hand sides in %.2f ms (%d of %zu trajectories with status 0)\n", covariance_steps,
                         rhs, 1e3 * t_cov, cov.n_ok, N);
+            if (covariance_hold_node)
+                std::printf("Covariance hold: node (the sweep of the loop that holds its correction over a segment)\n");
         }
 
         // the starts: `samples` per trajectory, the first of each the state its trajectory was solved for

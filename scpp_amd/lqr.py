@@ -73,7 +73,8 @@ class LQRTracker:
     keeps P(t_k) (the `riccati` property, [B][K][nx][nx]).
     horizon="discrete": the gains of a loop that changes its correction only at the nodes and holds it over a segment (track(hold="node")
     flies it): the discrete Riccati recursion over the segments' transition matrices [Phi | Gamma], from P_{K-1} = Qf as above, with stage
-    weights Q dt and R dt, discrete_steps RKF78 steps per segment; keep_discrete=True also keeps P, Phi and Gamma (discrete())."""
+    weights Q dt and R dt, discrete_steps RKF78 steps per segment; keep_discrete=True also keeps P, Phi and Gamma (discrete());
+    covariance(hold="node") is the dispersion analysis of that loop."""
 
     def __init__(self, model, X, U, t, state_weights=None, input_weights=None, par=None, device=0, library=None, compute=True,
                  horizon="infinite", terminal_weights=None, riccati_steps=5, keep_riccati=False, discrete_steps=5, keep_discrete=False):
@@ -224,13 +225,18 @@ class LQRTracker:
             out["record"] = self.ctx.track_record()
         return out
 
-    def covariance(self, sigma0, disturbance=None, steps=5, keep=False):
-        """Linear covariance analysis of the closed loop under the gains held, one forward sweep per trajectory on the device:
-        dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0 ([nx][nx] for every trajectory or [B][nx][nx], symmetric), A_cl = A - B K_t,
-        W = diag(disturbance) (None: 0), `steps` RKF78 steps per segment.  Returns state_std [B][K][nx], input_cov [B][K][nu][nu]
-        (G[k] S(t_k) G[k]'), final_cov [B][nx][nx], status [B], n_ok and, with keep=True, cov [B][K][nx][nx]."""
+    def covariance(self, sigma0, disturbance=None, steps=5, keep=False, hold="step"):
+        """Linear covariance analysis of the closed loop under the gains held, one forward sweep per trajectory on the device.
+        hold="step" (the default), the continuous loop: dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0 ([nx][nx] for every trajectory or
+        [B][nx][nx], symmetric), A_cl = A - B K_t, W = diag(disturbance) (None: 0), `steps` RKF78 steps per segment.
+        hold="node", the loop track(hold="node") flies, du_i = -G[i] dx(t_i) held over segment i: S_{i+1} = Acl_i S_i Acl_i' + Wd_i with
+        Acl_i = Phi_i - Gamma_i G[i] from the segment's transition matrices and Wd_i the disturbance the segment accumulates in open loop.
+        Returns state_std [B][K][nx], input_cov [B][K][nu][nu] (G[k] S(t_k) G[k]'), final_cov [B][nx][nx], status [B], n_ok and, with
+        keep=True, cov [B][K][nx][nx]."""
+        if hold not in ("step", "node"):
+            raise ValueError(f"hold = {hold!r}: 'step' or 'node'")
         self.ctx.set_covariance_inputs(sigma0, disturbance)
-        n_ok = self.ctx.propagate_covariance(steps, keep)
+        n_ok = self.ctx.propagate_covariance_discrete(steps, keep) if hold == "node" else self.ctx.propagate_covariance(steps, keep)
         out = self.ctx.download_covariance(keep)
         out["n_ok"] = n_ok
         return out

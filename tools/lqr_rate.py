@@ -1,7 +1,8 @@
 """LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
-    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--out FILE]
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--covariance-discrete STEPS]
+                              [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
 segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
@@ -25,6 +26,13 @@ others 1 % (Gaussian, fixed seed) off that state.  It only ADDS the key samples_
 held over a segment (track(hold="node")).  It only ADDS keys (discrete_*): the sweep's wall time, transition right-hand sides/s, the status
 counts and the flights.
 
+--covariance-discrete STEPS (measure(covariance_discrete=STEPS)) adds, last of all, the covariance sweep of the loop that holds its correction
+over a segment (LQRTracker.covariance(hold="node"), STEPS RKF78 steps per segment for the transition matrices and for the accumulated
+disturbance) under the gains the tracker holds at that point: the sampled-data gains when --discrete is given too.  Inputs as the covariance
+leg's.  It only ADDS keys (covariance_discrete_*): the sweep's wall time, right-hand sides/s (one counted per stage; with a disturbance every
+stage evaluates the Jacobian twice), the status counts and the final position standard deviation, next to the continuous sweep's under the
+same gains and inputs in the same run (covariance_discrete_continuous_*).
+
 The flight call of the saturate and samples legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
 best of --repeat.
 """
@@ -41,7 +49,8 @@ import numpy as np  # noqa: E402
 import scpp_amd  # noqa: E402
 
 
-def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None):
+def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None,
+            covariance_discrete=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -74,6 +83,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
         ric.update(covariance_leg(trk, int(covariance), repeat, "riccati" if riccati else "frozen"))
     if discrete:
         ric.update(discrete_leg(trk, x0, int(discrete), repeat))
+    if covariance_discrete:
+        ric.update(covariance_discrete_leg(trk, int(covariance_discrete), repeat, "discrete" if discrete else "riccati" if riccati else "frozen"))
     trk.close()
     fin = out["status"] != -2
     e = out["err1"][fin]
@@ -248,6 +259,40 @@ def covariance_leg(trk, steps, repeat, law):
     }
 
 
+def covariance_discrete_leg(trk, steps, repeat, law):
+    """the covariance sweep of the held loop on the tracker's trajectories under the gains it holds, and the continuous sweep next to it"""
+    sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
+    sigma0, w = np.diag(sd * sd), 0.01 * sd * sd
+    trk.ctx.set_covariance_inputs(sigma0, w)
+
+    def timed(sweep):
+        sweep(steps)  # warm
+        tc = []
+        for _ in range(repeat):
+            t = time.perf_counter()
+            n_ok = sweep(steps)  # returns after the status of every trajectory is on the host
+            tc.append(time.perf_counter() - t)
+        o = trk.ctx.download_covariance()
+        ok = o["status"] != -2
+        pos = np.sqrt((o["state_std"][ok, -1, 1:4] ** 2).sum(axis=1))  # RocketQuat: states 1..3 are the position
+        return min(tc), n_ok, o, [float(v) for v in np.percentile(pos, [5, 50, 95])] if pos.size else []
+
+    t_c, ok_c, _, pos_c = timed(trk.ctx.propagate_covariance)
+    t_d, ok_d, o, pos_d = timed(trk.ctx.propagate_covariance_discrete)
+    st = o["status"]
+    rhs = trk.B * (trk.K - 1) * steps * 13
+    return {
+        "covariance_discrete_steps_per_segment": steps, "covariance_discrete_gains": law, "covariance_discrete_wall_s": t_d,
+        "covariance_discrete_rhs": int(rhs), "covariance_discrete_rhs_per_s": rhs / t_d, "covariance_discrete_trajectories": int(st.size),
+        "covariance_discrete_status_ok": int(ok_d), "covariance_discrete_status_gains_incomplete": int((st == 2).sum()),
+        "covariance_discrete_status_nonfinite": int((st == -2).sum()),
+        "covariance_discrete_nonfinite_values": int(sum((~np.isfinite(o[k])).sum() for k in ("state_std", "input_cov", "final_cov"))),
+        "covariance_discrete_final_position_std_p5_p50_p95": pos_d,
+        "covariance_discrete_continuous_wall_s": t_c, "covariance_discrete_continuous_status_ok": int(ok_c),
+        "covariance_discrete_continuous_final_position_std_p5_p50_p95": pos_c,
+    }
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8192)
@@ -257,10 +302,11 @@ if __name__ == "__main__":
     ap.add_argument("--saturate", action="store_true", help="the flights again with the model's input limits in the loop")
     ap.add_argument("--samples", default="", help="comma-separated flights per trajectory of the sample-fan legs, e.g. 1,4,16")
     ap.add_argument("--discrete", type=int, default=0, help="RKF78 steps per segment of the sampled-data leg (0: no such leg)")
+    ap.add_argument("--covariance-discrete", type=int, default=0, help="RKF78 steps per segment of the held loop's covariance leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
-                  samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete)
+                  samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete, covariance_discrete=a.covariance_discrete)
     line = json.dumps(res)
     print(line)
     if a.out:
