@@ -22,6 +22,8 @@
  *       (the covariance recursion of the loop that holds its correction)       scpp_hip_lqr_propagate_covariance_discrete
  *   nothing: the reference has no sampled-data controller                                     scpp_hip_lqr_compute_gains_discrete, _download_discrete,
  *       (the discrete Riccati recursion over the segments' transition matrices) scpp_hip_lqr_set_feedback_hold
+ *   nothing: the reference has no feedforward for a nominal that misses its nodes             scpp_hip_lqr_compute_gains_affine, _download_affine,
+ *       (the Riccati sweep on the state [e; 1])                                scpp_hip_lqr_set_feedforward_terms, _set_feedforward
  *
  * Deviations, all deliberate:
  *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
@@ -83,6 +85,26 @@
  *     symmetric to the bit, as for the continuous sweep.  With w NULL or all zero the M integration is skipped as a whole; the result is
  *     bitwise that of Wd = 0.
  *
+ *   - scpp_hip_lqr_compute_gains_affine is an addition: the finite-horizon law for a nominal that does not obey the dynamics.  One trajectory
+ *     has K nodes and flight time T, dt = T / (K - 1).  Inside segment i at fraction a in [0, 1] the reference is exactly the Riccati sweep's:
+ *     x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]), j = i+1 (first-order hold) or i (zero-order hold); the segment index is the
+ *     loop's and is never recomputed from a time.  The defect of the reference is c = f(x, u) - (X[i+1] - X[i]) / dt, f the plant's flow map
+ *     (SI parameters) on the full state of every model (RocketQuat: 14 states).  Along such a nominal the deviation of the loop
+ *     u = u_ref + du obeys de/dt = A e + B du + c(t).  The cost is that of the finite-horizon law, int e'Qe + du'R du dt + e(T)'Qf e(T); the value
+ *     function is V = e'P e + 2 p'e + s with
+ *         -dP/dt = A'P + P A - P B R^-1 B'P + Q          P(T) = Qf     (the Riccati sweep's own equation)
+ *         -dp/dt = (A - B R^-1 B'P)'p + P c               p(T) = 0
+ *         -ds/dt = 2 p'c - p'B R^-1 B'p                   s(T) = 0
+ *         du = -K e - k,   K_k = R^-1 B_k'P(t_k),   k_k = R^-1 B_k'p(t_k)      (B_k at (X[k], U[min(k, nU-1)]), as for the gains)
+ *     s(t_k) is the predicted cost-to-go of a flight that is exactly on the nominal at node k.  The three equations are ONE Riccati equation,
+ *     that of the state [e; 1] with A_aug = [[A, c], [0, 0]], B_aug = [B; 0], Q_aug = diag(Q, 0), Qf_aug = diag(Qf, 0) and
+ *     P_aug = [[P, p], [p', s]], and are integrated as such: the integrator, the stage positions and the construction that keeps the matrix
+ *     symmetric to the bit are those of scpp_hip_lqr_compute_gains_riccati.  P and K are those of that sweep at the same step count (the
+ *     augmentation adds products with exact zeros to them).  scpp_hip_lqr_set_feedforward(1) flies u_cmd = u_ref(t) - K_t (x - x_ref(t)) - k_t,
+ *     k_t interpolated with the indices and the fraction of the gain.  The loop that holds its correction over a segment
+ *     (scpp_hip_lqr_set_feedback_hold(1)) has no such term here: its optimal offset is an affine DISCRETE recursion, which is not built, and the
+ *     two together are refused.  The covariance sweeps describe the dispersion about the mean, which does not depend on c: they are valid under
+ *     either setting; the mean itself is not propagated.
  *   - input limits (scpp_hip_lqr_set_input_limits) are an addition to the tracking loop, off by default: with limits (T_min, T_max, angle_max)
  *     the loop applies u = sat(u_cmd), u_cmd = -K_t (x - x_ref) + u_ref computed as without them.  A non-finite u_cmd retires the flight with
  *     status -2 before sat.  Thrust-vector models (RocketQuat: u = (T_B, tau_z), sat acts on u[0..2] and u[3] passes through; Lander3dof:
@@ -155,6 +177,26 @@ extern "C"
     int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *ctx, int steps, int keep_p, int *n_ok);
     /* P [B][K][nx][nx] of the last sweep (zeros on failed nodes); SCPP_E_STATE unless the last gain computation was a sweep with keep_p != 0 */
     int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *ctx, double *P);
+    /* affine finite-horizon gains (the definition is above): one sweep of [[P, p], [p', s]] per trajectory from P(T) = Qf, p(T) = 0, s(T) = 0.
+       Preconditions and SCPP_E_* answers are those of scpp_hip_lqr_compute_gains_riccati.  Gains, status and the count land where
+       scpp_hip_lqr_download_gains reads them, the feedforward terms k_k where scpp_hip_lqr_download_affine does.  A trajectory with a
+       non-finite node, input or flight time gets SCPP_LQR_NONFINITE and zeros on every node; a P, p or s that turns non-finite in segment k (a
+       non-finite flow map at a finite reference point included) does the same for node k and every earlier node.  Nothing non-finite is ever
+       written.  keep != 0 also keeps P, p and s of every node (allocated on the first such request).  *n_ok (optional) = nodes with status 0. */
+    int scpp_hip_lqr_compute_gains_affine(scpp_hip_lqr_ctx *ctx, int steps, int keep, int *n_ok);
+    /* ff [B][K][nu] = k_k, P [B][K][nx][nx], p [B][K][nx], s [B][K] of the last affine sweep (zeros on failed nodes); any pointer may be NULL.
+       SCPP_E_STATE unless the last gain computation was scpp_hip_lqr_compute_gains_affine, and for P, p, s after a sweep with keep == 0. */
+    int scpp_hip_lqr_download_affine(scpp_hip_lqr_ctx *ctx, double *ff /* [B][K][nu] */, double *P, double *p /* [B][K][nx] */, double *s /* [B][K] */);
+    /* user-supplied feedforward terms [B][K][nu] for the gains the context holds (computed or scpp_hip_lqr_set_gains); non-finite entries are
+       refused (SCPP_E_ARG); SCPP_E_STATE without gains.  Feedforward terms, computed or supplied, are invalidated by new trajectories, flow
+       parameters, scpp_hip_lqr_set_gains and every scpp_hip_lqr_compute_gains* other than the affine one. */
+    int scpp_hip_lqr_set_feedforward_terms(scpp_hip_lqr_ctx *ctx, const double *ff /* [B][K][nu] */);
+    /* whether the tracking loop applies the feedforward term.  mode 0 (the default): the loop as it is without one.  mode 1:
+       u_cmd = u_ref(t) - K_t (x - x_ref(t)) - k_t, k_t = ff[i] + a (ff[j] - ff[i]) with the indices and the fraction of the gain; flight f of a
+       sample fan reads the row of trajectory f / samples; input limits, the record, the stop tolerance and the non-finite retirement act on this
+       u_cmd.  Anything else: SCPP_E_ARG.  Under mode 1 scpp_hip_lqr_track / _track_samples return SCPP_E_STATE when the context holds no
+       feedforward terms and SCPP_E_UNSUPPORTED when the feedback hold is 1.  The mode stays until it is set again. */
+    int scpp_hip_lqr_set_feedforward(scpp_hip_lqr_ctx *ctx, int mode);
     /* sampled-data gains (the definition is above): one discrete Riccati recursion per trajectory from P_{K-1} = Qf
        (scpp_hip_lqr_set_terminal_weights; default Q), steps >= 1 RKF78 steps per segment for [Phi | Gamma] (SCPP_E_ARG otherwise).  Gains,
        status and the count land where scpp_hip_lqr_download_gains reads them (the count: RKF78 steps behind the node, (K-1-k) steps); node

@@ -487,6 +487,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_set_input_limits", "scpp_hip_lqr_track_samples", "scpp_hip_lqr_track_download_saturation",
     "scpp_hip_lqr_compute_gains_discrete", "scpp_hip_lqr_download_discrete", "scpp_hip_lqr_set_feedback_hold",
     "scpp_hip_lqr_propagate_covariance_discrete",
+    "scpp_hip_lqr_compute_gains_affine", "scpp_hip_lqr_download_affine", "scpp_hip_lqr_set_feedforward_terms", "scpp_hip_lqr_set_feedforward",
 ]
 _lqr_libs = {}
 
@@ -586,6 +587,29 @@ class LqrContext:
         P = np.zeros((self.B, self.K, self.nx, self.nx))
         _chk(self.lib.scpp_hip_lqr_download_riccati(self.h, _p(P)), "lqr_download_riccati")
         return P
+
+    def compute_gains_affine(self, steps=5, keep=False):
+        """affine finite-horizon gains and feedforward terms (one sweep of [[P, p], [p', s]] per trajectory); returns the number of nodes
+        with status 0"""
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_compute_gains_affine(self.h, int(steps), int(bool(keep)), C.byref(n)), "lqr_compute_gains_affine")
+        return int(n.value)
+
+    def download_affine(self, kept=False):
+        """ff [B][K][nu] of the last affine sweep and, with kept=True (a sweep with keep=True), P [B][K][nx][nx], p [B][K][nx], s [B][K]"""
+        out = dict(ff=np.zeros((self.B, self.K, self.nu)))
+        if kept:
+            out.update(P=np.zeros((self.B, self.K, self.nx, self.nx)), p=np.zeros((self.B, self.K, self.nx)), s=np.zeros((self.B, self.K)))
+        _chk(self.lib.scpp_hip_lqr_download_affine(self.h, *[_p(out.get(k)) for k in ("ff", "P", "p", "s")]), "lqr_download_affine")
+        return out
+
+    def set_feedforward_terms(self, ff):
+        ff = np.ascontiguousarray(ff, dtype=np.float64).reshape(self.B, self.K, self.nu)
+        _chk(self.lib.scpp_hip_lqr_set_feedforward_terms(self.h, _p(ff)), "lqr_set_feedforward_terms")
+
+    def set_feedforward(self, mode):
+        """0: the loop without a feedforward term (the default); 1: u_cmd = u_ref - K_t (x - x_ref) - k_t"""
+        _chk(self.lib.scpp_hip_lqr_set_feedforward(self.h, int(mode)), "lqr_set_feedforward")
 
     def compute_gains_discrete(self, steps=5, keep=False):
         """sampled-data gains (one discrete Riccati recursion per trajectory); returns the number of nodes with status 0"""

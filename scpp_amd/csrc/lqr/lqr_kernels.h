@@ -1,9 +1,10 @@
 // Batched LQR trajectory tracking: the two kernels behind include/scpp_hip_lqr.h.
 //   lqr_gain_kernel<Plugin>   one frozen-time LQR gain per (trajectory, node): replaces LQRTracker::LQRTracker (LQRTracker.cpp:6-28) and
 //                             ComputeLQR / careSolve / solveSchurIterative (LQR.cpp:7-109)
-//   lqr_track_kernel<Plugin, SAT, HOLD>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
+//   lqr_track_kernel<Plugin, SAT, HOLD, FF>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
 //                             LQRTracker::getInput / interpolateGains (LQRTracker.cpp:43-65) and trajectoryData.hpp:41-78; SAT: with the
 //                             plugin's input limits in the loop (the clip of LQR_sim.cpp:55-66)
+//                             FF: with the feedforward term of the affine finite-horizon law (lqr_affine_kernel.h)
 // A component of its own: it reads the model plugins' flow maps, their generated Jacobian rows and the RKF78 tableau (csrc/common.h) and nothing
 // else of the solver; the solver's sources are not touched by it.
 #pragma once
@@ -467,15 +468,21 @@ __global__ void __launch_bounds__(WAVE) lqr_gain_kernel(long nodes, int K, int n
 //   HOLD: the feedback term is held over a segment (scpp_hip_lqr_set_feedback_hold): du = -G[i] (x - x_ref(t)) is latched at the first plant step
 //   whose segment index i differs from the latched one (flight start included) and u_cmd = u_ref(t) + du on every plant step; everything else as
 //   without it.  HOLD == false is the loop as it was.
-template <class P, bool SAT, bool HOLD = false>
+//   FF: the affine law's second term (scpp_hip_lqr_set_feedforward): u_cmd = u_ref(t) - K_t (x - x_ref(t)) - k_t with k_t = ff[i] + a (ff[iu1] - ff[i]),
+//   ff [B][K][nu] the row of the flight's trajectory, interpolated with the indices and the fraction of the gain; limits, record, stop tolerance
+//   and the non-finite retirement act on this u_cmd.  FF == false reads no ff and is the loop as it was; FF with HOLD is not defined (the host
+//   refuses it).
+template <class P, bool SAT, bool HOLD = false, bool FF = false>
 __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int K, int nU, int uRows, const double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ T,
                                  const double *__restrict__ par, int par_stride, const double *__restrict__ G,
                                  const double *__restrict__ x_start, const double *__restrict__ x_final, double time_step, int substeps,
                                  double stop_tol, int max_steps, int n_record, int write_steps, int rec_cap, double *__restrict__ out_x,
                                  double *__restrict__ out_u, double *__restrict__ out_s, int *__restrict__ out_i, double *__restrict__ rec_x,
                                  double *__restrict__ rec_u, double *__restrict__ rec_t, int *__restrict__ rec_n,
-                                 const double *__restrict__ lim, int lim_stride, int *__restrict__ out_nsat, double *__restrict__ out_clip)
+                                 const double *__restrict__ lim, int lim_stride, int *__restrict__ out_nsat, double *__restrict__ out_clip,
+                                 const double *__restrict__ ff)
 {
+    static_assert(!(FF && HOLD), "the held loop's offset is another recursion");
     using Model = typename P::Model;
     constexpr int NX = Model::NX, NU = Model::NU, NP = Model::NP;
     const long b = long(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -573,6 +580,12 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int
                     acc += (g0 + a * (g1 - g0)) * dx[j];
                 }
                 un[c] = -acc + (u0 + a * (u1 - u0));
+                if constexpr (FF)
+                {
+                    const double *Fb = ff + tr * K * NU;
+                    const double f0 = Fb[i * NU + c], f1 = Fb[iu1 * NU + c];
+                    un[c] = un[c] - (f0 + a * (f1 - f0));
+                }
             }
         }
         bool ufin = true;

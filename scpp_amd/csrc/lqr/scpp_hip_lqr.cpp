@@ -3,9 +3,14 @@
 #include "../../../include/scpp_hip_lqr.h"
 #include "lqr_kernels.h"
 #include "lqr_riccati_kernel.h"
+#include "lqr_affine_launch.h"
 #include "lqr_covariance_kernel.h"
 #include "lqr_discrete_kernel.h"
 #include "lqr_covariance_discrete_kernel.h"
+
+#ifdef SCPP_HIP_EMU
+#include "scpp_hip_lqr_affine.cpp" // the emulation is one translation unit (its fiber switch is a global symbol of the emulation header)
+#endif
 
 #include <cmath>
 #include <cstdlib>
@@ -54,6 +59,12 @@ struct scpp_hip_lqr_ctx
     size_t phi_cap = 0, gam_cap = 0;
     bool have_disc = false;
     int hold = 0; // scpp_hip_lqr_set_feedback_hold
+    // affine sweep (scpp_hip_lqr_compute_gains_affine): the feedforward terms k_k, allocated by the first sweep or the first
+    // scpp_hip_lqr_set_feedforward_terms; P lands in the buffer above, p and s in two of their own, allocated by the first keep request
+    double *ff = nullptr, *ap = nullptr, *as = nullptr;
+    size_t ff_cap = 0, ap_cap = 0, as_cap = 0;
+    bool have_ff = false, have_affine = false, affine_kept = false; // terms held; the last gain computation was the affine sweep; with keep
+    int ffmode = 0;                                                  // scpp_hip_lqr_set_feedforward
     int *gstatus = nullptr, *giters = nullptr;
     // covariance sweep (scpp_hip_lqr_propagate_covariance): inputs and outputs are allocated by the first scpp_hip_lqr_set_covariance_inputs,
     // the full S(t_k) by the first keep_cov request
@@ -126,7 +137,11 @@ static bool allFinite(const double *v, size_t n)
 }
 
 // whatever changes the trajectories or replaces the gains: no gains, no P, no covariance
-static void invalidateGains(scpp_hip_lqr_ctx *c) { c->have_gains = c->gains_computed = c->have_p = c->have_disc = c->have_cov = false; }
+static void invalidateGains(scpp_hip_lqr_ctx *c)
+{
+    c->have_gains = c->gains_computed = c->have_p = c->have_disc = c->have_cov = false;
+    c->have_ff = c->have_affine = c->affine_kept = false;
+}
 
 // a change of weights or parameters: gains the library computed are stale, gains the caller supplied (scpp_hip_lqr_set_gains) stay
 static void invalidateComputedGains(scpp_hip_lqr_ctx *c)
@@ -335,7 +350,7 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam};
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -389,6 +404,7 @@ int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
     c->par_rows = B;
     c->have_par = true;
     c->have_cov = false;
+    c->have_ff = c->have_affine = c->affine_kept = false; // the defect of the nominal is one of THIS plant
     invalidateComputedGains(c);
     return SCPP_OK;
 }
@@ -444,6 +460,7 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
         return rc;
     c->have_gains = c->gains_computed = true;
     c->have_p = c->have_disc = c->have_cov = false;
+    c->have_ff = c->have_affine = c->affine_kept = false;
     return countOk(c, c->gstatus, size_t(nodes), n_ok);
 }
 
@@ -477,6 +494,7 @@ int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *c, int steps, int keep_
     const long nodes = long(c->B) * c->K;
     const size_t p_need = size_t(nodes) * c->nx * c->nx;
     c->have_p = c->have_disc = false;
+    c->have_ff = c->have_affine = c->affine_kept = false;
     if (keep_p)
         if (int rc = growTo(c, &c->P, &c->P_cap, p_need))
             return rc;
@@ -506,6 +524,89 @@ int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *c, double *P)
     return SCPP_OK;
 }
 
+int scpp_hip_lqr_compute_gains_affine(scpp_hip_lqr_ctx *c, int steps, int keep, int *n_ok)
+{
+    if (!c || steps < 1)
+        return SCPP_E_ARG;
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (long(c->K - 1) * steps > 0x7fffffffL)
+        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
+    DeviceGuard guard(c->device);
+    const long nodes = long(c->B) * c->K;
+    c->have_p = c->have_disc = false;
+    c->have_ff = c->have_affine = c->affine_kept = false;
+    if (int rc = growTo(c, &c->ff, &c->ff_cap, size_t(c->Bmax) * c->K * c->nu))
+        return rc;
+    if (keep)
+    {
+        if (int rc = growTo(c, &c->P, &c->P_cap, size_t(nodes) * c->nx * c->nx))
+            return rc;
+        if (int rc = growTo(c, &c->ap, &c->ap_cap, size_t(nodes) * c->nx))
+            return rc;
+        if (int rc = growTo(c, &c->as, &c->as_cap, size_t(nodes)))
+            return rc;
+    }
+    if (!launchAffineSweep(c->model, c->stream, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par, c->par_stride, c->q, c->r,
+                           c->have_qf ? c->qf : c->q, c->G, c->gstatus, c->giters, c->ff, keep ? c->P : nullptr, keep ? c->ap : nullptr,
+                           keep ? c->as : nullptr))
+        return SCPP_E_ARG;
+    if (hipGetLastError() != hipSuccess)
+        return SCPP_E_HIP;
+    c->have_gains = c->gains_computed = true;
+    c->have_ff = c->have_affine = true;
+    c->affine_kept = keep != 0;
+    c->have_cov = false;
+    return countOk(c, c->gstatus, size_t(nodes), n_ok);
+}
+
+int scpp_hip_lqr_download_affine(scpp_hip_lqr_ctx *c, double *ff, double *P, double *p, double *s)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_affine || ((P || p || s) && !c->affine_kept))
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t nodes = size_t(c->B) * c->K, nx = size_t(c->nx);
+    if (ff)
+        CHECK_HIP(hipMemcpyAsync(ff, c->ff, nodes * c->nu * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (P)
+        CHECK_HIP(hipMemcpyAsync(P, c->P, nodes * nx * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (p)
+        CHECK_HIP(hipMemcpyAsync(p, c->ap, nodes * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (s)
+        CHECK_HIP(hipMemcpyAsync(s, c->as, nodes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_feedforward_terms(scpp_hip_lqr_ctx *c, const double *ff)
+{
+    if (!c || !ff)
+        return SCPP_E_ARG;
+    if (!c->have_gains)
+        return SCPP_E_STATE;
+    const size_t n = size_t(c->B) * c->K * c->nu;
+    if (!allFinite(ff, n))
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    if (int rc = growTo(c, &c->ff, &c->ff_cap, size_t(c->Bmax) * c->K * c->nu))
+        return rc;
+    CHECK_HIP(hipMemcpyAsync(c->ff, ff, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    c->have_ff = true;
+    c->have_affine = c->affine_kept = false; // the terms are the caller's now: scpp_hip_lqr_download_affine has nothing of its own left
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_feedforward(scpp_hip_lqr_ctx *c, int mode)
+{
+    if (!c || (mode != 0 && mode != 1))
+        return SCPP_E_ARG;
+    c->ffmode = mode;
+    return SCPP_OK;
+}
+
 int scpp_hip_lqr_compute_gains_discrete(scpp_hip_lqr_ctx *c, int steps, int keep, int *n_ok)
 {
     if (!c || steps < 1)
@@ -518,6 +619,7 @@ int scpp_hip_lqr_compute_gains_discrete(scpp_hip_lqr_ctx *c, int steps, int keep
     const long nodes = long(c->B) * c->K;
     const size_t segs = size_t(c->B) * (c->K - 1);
     c->have_p = c->have_disc = false;
+    c->have_ff = c->have_affine = c->affine_kept = false;
     if (keep)
     {
         if (int rc = growTo(c, &c->P, &c->P_cap, size_t(nodes) * c->nx * c->nx))
@@ -755,6 +857,13 @@ int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *c, const double *x_start, const
         return SCPP_E_STATE; // no gains, or limits for another number of trajectories
     if (Btraj != c->B)
         return SCPP_E_ARG; // `samples` starts per trajectory
+    if (c->ffmode)
+    {
+        if (!c->have_ff)
+            return SCPP_E_STATE; // no feedforward terms to fly
+        if (c->hold)
+            return SCPP_E_UNSUPPORTED; // the held loop's offset is another recursion
+    }
     if (!allFinite(x_final, size_t(c->nx)))
         return SCPP_E_ARG;
     const int B = Btraj * samples; // flights
@@ -796,9 +905,17 @@ int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *c, const double *x_start, const
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), 0, c->stream, B, samples, c->K, c->nU, c->uRows, c->tX, c->tU, c->tT,
                                (const double *)c->par, c->par_stride, (const double *)c->G, (const double *)c->xs, (const double *)c->xf, time_step,
                                substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                               (const double *)c->lim, c->lim_rows == 1 ? 0 : LIM_ROW, c->onsat, c->oclip);
+                               (const double *)c->lim, c->lim_rows == 1 ? 0 : LIM_ROW, c->onsat, c->oclip,
+                               (const double *)(c->ffmode ? c->ff : nullptr));
         };
-        if (c->hold)
+        if (c->ffmode)
+        {
+            if (c->have_lim)
+                go(lqr_track_kernel<P, true, false, true>);
+            else
+                go(lqr_track_kernel<P, false, false, true>);
+        }
+        else if (c->hold)
         {
             if (c->have_lim)
                 go(lqr_track_kernel<P, true, true>);

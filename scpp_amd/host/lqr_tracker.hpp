@@ -37,6 +37,10 @@ struct lqr_track_result_t
 // (scpp_hip_lqr_compute_gains_discrete; LQRTracker::setFeedbackHold flies such a loop): the discrete Riccati recursion over the segments'
 // transition matrices from P_{K-1} = Qf (terminal_weights as above), discrete_steps RKF78 steps per segment; keep_discrete: P, Phi and Gamma are
 // downloaded into LQRTracker::discrete_P, discrete_Phi, discrete_Gamma.
+// affine = true (the other two must then be false): the finite-horizon law for a nominal that does not obey the dynamics
+// (scpp_hip_lqr_compute_gains_affine): the Riccati sweep on the state [e; 1], which also yields the feedforward terms k_k of du = -K e - k, from
+// P(T) = Qf (terminal_weights as above), affine_steps RKF78 steps per segment; the terms are downloaded into LQRTracker::feedforward and
+// track() applies them (LQRTracker::setFeedforward(false) flies without); keep_affine: P, p and s are downloaded into affine_P, affine_p, affine_s.
 struct lqr_gain_options_t
 {
     bool finite_horizon = false;
@@ -46,6 +50,9 @@ struct lqr_gain_options_t
     bool discrete = false;
     int discrete_steps = 5;
     bool keep_discrete = false;
+    bool affine = false;
+    int affine_steps = 5;
+    bool keep_affine = false;
 };
 
 // the closed-loop covariance sweep (scpp_hip_lqr_propagate_covariance): dS/dt = A_cl S + S A_cl' + W, S(0) = sigma0, under the gains the tracker
@@ -114,9 +121,28 @@ public:
             t[size_t(b)] = td.t;
         }
         check(scpp_hip_lqr_set_trajectories(ctx, X.data(), U.data(), t.data(), B), "scpp_hip_lqr_set_trajectories");
-        if (opts.finite_horizon && opts.discrete)
-            throw std::invalid_argument("LQRTracker: finite_horizon and discrete are two gain laws, choose one");
-        if (opts.discrete)
+        if (int(opts.finite_horizon) + int(opts.discrete) + int(opts.affine) > 1)
+            throw std::invalid_argument("LQRTracker: finite_horizon, discrete and affine are three gain laws, choose one");
+        if (opts.affine)
+        {
+            std::vector<double> qf = opts.terminal_weights.empty() ? loadTerminalWeights() : opts.terminal_weights;
+            if (!qf.empty() && qf.size() != NX)
+                throw std::invalid_argument("LQRTracker: terminal_weights needs one entry per state");
+            check(scpp_hip_lqr_set_terminal_weights(ctx, qf.empty() ? nullptr : qf.data()), "scpp_hip_lqr_set_terminal_weights");
+            check(scpp_hip_lqr_compute_gains_affine(ctx, opts.affine_steps, opts.keep_affine ? 1 : 0, &n_ok), "scpp_hip_lqr_compute_gains_affine");
+            feedforward.resize(size_t(B) * K * NU);
+            if (opts.keep_affine)
+            {
+                affine_P.resize(size_t(B) * K * NX * NX);
+                affine_p.resize(size_t(B) * K * NX);
+                affine_s.resize(size_t(B) * K);
+            }
+            check(scpp_hip_lqr_download_affine(ctx, feedforward.data(), opts.keep_affine ? affine_P.data() : nullptr,
+                                               opts.keep_affine ? affine_p.data() : nullptr, opts.keep_affine ? affine_s.data() : nullptr),
+                  "scpp_hip_lqr_download_affine");
+            setFeedforward(true);
+        }
+        else if (opts.discrete)
         {
             std::vector<double> qf = opts.terminal_weights.empty() ? loadTerminalWeights() : opts.terminal_weights;
             if (!qf.empty() && qf.size() != NX)
@@ -224,6 +250,11 @@ public:
             for (size_t c = 0; c < NX; c++)
                 acc += K[r][c] * (x[c] - (td.X[i][c] + a * (td.X[i + 1][c] - td.X[i][c])));
             u[r] = -acc + (td.U[i][r] + a * (td.U[j][r] - td.U[i][r]));
+            if (feedforward_on)
+            {
+                const double f0 = feedforward[(b * td.n_X() + i) * NU + r], f1 = feedforward[(b * td.n_X() + j) * NU + r];
+                u[r] -= f0 + a * (f1 - f0);
+            }
         }
     }
 
@@ -245,6 +276,16 @@ public:
     // when the loop updates its feedback term (scpp_hip_lqr_set_feedback_hold): false (the default) on every plant step, true: latched at each
     // node and held over the segment, the loop the discrete gain law designs for.  Stays until it is set again.
     void setFeedbackHold(bool node) { check(scpp_hip_lqr_set_feedback_hold(ctx, node ? 1 : 0), "scpp_hip_lqr_set_feedback_hold"); }
+    // whether the loop applies the feedforward term of the affine law (scpp_hip_lqr_set_feedforward): u_cmd = u_ref - K_t (x - x_ref) - k_t.  On
+    // after an affine sweep, off otherwise; needs the terms of such a sweep, and is refused together with setFeedbackHold(true) by track().
+    void setFeedforward(bool on)
+    {
+        if (on && feedforward.empty())
+            throw std::invalid_argument("LQRTracker::setFeedforward: no feedforward terms held (lqr_gain_options_t::affine)");
+        check(scpp_hip_lqr_set_feedforward(ctx, on ? 1 : 0), "scpp_hip_lqr_set_feedforward");
+        feedforward_on = on;
+    }
+    bool feedforwardOn() const { return feedforward_on; }
     // regulator mode (scpp_hip_lqr_set_stop_tolerance) and user-supplied gains [B][K], for LQRAlgorithm::simulate
     void setStopTolerance(double tol) { check(scpp_hip_lqr_set_stop_tolerance(ctx, tol), "scpp_hip_lqr_set_stop_tolerance"); }
     void setGains(const std::vector<feedback_matrix_t> &G)
@@ -253,6 +294,9 @@ public:
             throw std::invalid_argument("LQRTracker::setGains: one gain per trajectory and node");
         check(scpp_hip_lqr_set_gains(ctx, &G[0][0][0]), "scpp_hip_lqr_set_gains");
         gains = G;
+        if (feedforward_on)
+            setFeedforward(false); // the terms went with the gains they belonged to
+        feedforward.clear();
     }
 
     // SC_tracking.cpp:48-75 for every trajectory at once, on the device: `samples` flights per trajectory, flight f from x_start[f] along
@@ -355,6 +399,8 @@ public:
     std::vector<int32_t> status, iterations; // iterations: sign iterations, or RKF78 steps behind the node (finite horizon, discrete)
     std::vector<double> riccati;             // [B][K][NX][NX], finite horizon with keep_riccati only
     std::vector<double> discrete_P, discrete_Phi, discrete_Gamma; // [B][K][NX][NX], [B][K-1][NX][NX], [B][K-1][NX][NU]: discrete with keep_discrete only
+    std::vector<double> feedforward;                 // [B][K][NU] = k_k: affine only
+    std::vector<double> affine_P, affine_p, affine_s; // [B][K][NX][NX], [B][K][NX], [B][K]: affine with keep_affine only
     lqr_gain_options_t opts;
 
 private:
@@ -367,6 +413,7 @@ private:
     std::vector<trajectory_data_t> tds;
     scpp_hip_lqr_ctx *ctx = nullptr;
     int n_ok = 0;
+    bool feedforward_on = false;
 };
 
 } // namespace scpp

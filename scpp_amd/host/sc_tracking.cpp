@@ -3,10 +3,14 @@
 //                         flown along it from x_init                                              (what the reference does)
 //   --batch N [--seed S]: N randomised initial states: N trajectories, N x K gains, N flights from those initial states
 //   --config DIR --out DIR --K n --device d --time-step s
-//   --gains frozen|riccati|discrete : frozen (default): one frozen-time infinite-horizon gain per node (the reference's); riccati: finite-horizon gains,
+//   --gains frozen|riccati|discrete|affine : frozen (default): one frozen-time infinite-horizon gain per node (the reference's); riccati: finite-horizon gains,
 //                         the differential Riccati equation swept backwards along each trajectory; --riccati-steps n RKF78 steps per segment (5)
 //                         discrete: sampled-data gains, the discrete Riccati recursion over the segments' transition matrices
 //                         (scpp_hip_lqr_compute_gains_discrete); --discrete-steps n RKF78 steps per segment (5)
+//                         affine: the finite-horizon law for a nominal that misses its own nodes (scpp_hip_lqr_compute_gains_affine): the riccati
+//                         gains and a feedforward term against the nominal's defect, which the loop applies; --affine-steps n RKF78 steps
+//                         per segment (5); --no-feedforward flies the same gains without the term (the flights of --gains riccati).
+//                         Writes feedforward.txt (one node per row) of instance 0 next to X.txt
 //   --hold step|node    : step (default): the feedback term changes on every plant step; node: it is latched at each node and held over the
 //                         segment (scpp_hip_lqr_set_feedback_hold), the loop --gains discrete designs for
 //   --covariance        : also the closed-loop covariance sweep along every trajectory under those gains (scpp_hip_lqr_propagate_covariance):
@@ -46,7 +50,7 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
-    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false;
+    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false, no_feedforward = false;
     int covariance_steps = 5, samples = 1;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
@@ -77,14 +81,19 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--gains"))
         {
             const std::string which = next();
-            if (which != "frozen" && which != "riccati" && which != "discrete")
+            if (which != "frozen" && which != "riccati" && which != "discrete" && which != "affine")
             {
-                std::fprintf(stderr, "--gains %s: frozen, riccati or discrete\n", which.c_str());
+                std::fprintf(stderr, "--gains %s: frozen, riccati, discrete or affine\n", which.c_str());
                 return 2;
             }
             gain_opts.finite_horizon = which == "riccati";
             gain_opts.discrete = which == "discrete";
+            gain_opts.affine = which == "affine";
         }
+        else if (!std::strcmp(argv[i], "--affine-steps"))
+            gain_opts.affine_steps = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--no-feedforward"))
+            no_feedforward = true;
         else if (!std::strcmp(argv[i], "--discrete-steps"))
             gain_opts.discrete_steps = std::atoi(next());
         else if (!std::strcmp(argv[i], "--hold"))
@@ -166,6 +175,9 @@ int main(int argc, char **argv)
         if (gain_opts.finite_horizon)
             std::printf("Gains: riccati (finite horizon, %d RKF78 steps per segment, %zu Riccati right-hand sides)\n", gain_opts.riccati_steps,
                         N * (r.td[0].n_X() - 1) * size_t(gain_opts.riccati_steps) * 13);
+        else if (gain_opts.affine)
+            std::printf("Gains: affine (finite horizon with feedforward, %d RKF78 steps per segment, %zu Riccati right-hand sides on [e; 1])\n",
+                        gain_opts.affine_steps, N * (r.td[0].n_X() - 1) * size_t(gain_opts.affine_steps) * 13);
         else if (gain_opts.discrete)
             std::printf("Gains: discrete (sampled data, %d RKF78 steps per segment, %zu transition right-hand sides)\n", gain_opts.discrete_steps,
                         N * (r.td[0].n_X() - 1) * size_t(gain_opts.discrete_steps) * 13);
@@ -213,6 +225,8 @@ int main(int argc, char **argv)
         if (saturate)
             tracker.setInputLimitsFromModel();
         tracker.setFeedbackHold(hold_node);
+        if (gain_opts.affine && no_feedforward)
+            tracker.setFeedforward(false);
 
         // start simulation
         scpp::lqr_track_result_t sim;
@@ -232,6 +246,8 @@ int main(int argc, char **argv)
                     sim.steps[0] + 1, steps, 1e3 * t_run, double(steps) / t_run, sim.n_finite, F);
         std::printf("Hold: %s\n", hold_node ? "node (the feedback term is latched at each node and held over the segment)"
                                             : "step (the feedback term changes on every plant step)");
+        if (gain_opts.affine)
+            std::printf("Feedforward: %s\n", tracker.feedforwardOn() ? "on (u_cmd = u_ref - K_t (x - x_ref) - k_t)" : "off (--no-feedforward: the riccati loop)");
         if (samples > 1)
             std::printf("Sample fan: %d flights per trajectory, %zu flights\n", samples, F);
         if (saturate)
@@ -258,6 +274,16 @@ int main(int argc, char **argv)
             std::ofstream f(outputPath / "t.txt");
             for (double t : sim.t_sim.at(0))
                 f << t << "\n";
+        }
+        if (gain_opts.affine)
+        {
+            // k_k of instance 0, one node per row, round-trip precision
+            constexpr size_t NU = Model::input_dim;
+            std::ofstream ff(outputPath / "feedforward.txt");
+            ff.precision(17);
+            for (size_t k = 0; k < r.td[0].n_X(); k++)
+                for (size_t j = 0; j < NU; j++)
+                    ff << tracker.feedforward[k * NU + j] << (j + 1 < NU ? ", " : "\n");
         }
         if (saturate || samples > 1)
         {

@@ -74,14 +74,20 @@ class LQRTracker:
     horizon="discrete": the gains of a loop that changes its correction only at the nodes and holds it over a segment (track(hold="node")
     flies it): the discrete Riccati recursion over the segments' transition matrices [Phi | Gamma], from P_{K-1} = Qf as above, with stage
     weights Q dt and R dt, discrete_steps RKF78 steps per segment; keep_discrete=True also keeps P, Phi and Gamma (discrete());
-    covariance(hold="node") is the dispersion analysis of that loop."""
+    covariance(hold="node") is the dispersion analysis of that loop.
+    horizon="affine": the finite-horizon law for a nominal that does not obey the dynamics (a solver trajectory): the Riccati sweep on the state
+    [e; 1], which also yields the feedforward terms k_k of du = -K e - k against the nominal's defect c = f(x_ref, u_ref) - dx_ref/dt, from
+    P(T) = Qf as above, affine_steps RKF78 steps per segment; keep_affine=True also keeps P, p and s (affine()).  P and K are those of
+    horizon="finite" at the same step count; track() then applies the term unless told otherwise."""
 
     def __init__(self, model, X, U, t, state_weights=None, input_weights=None, par=None, device=0, library=None, compute=True,
-                 horizon="infinite", terminal_weights=None, riccati_steps=5, keep_riccati=False, discrete_steps=5, keep_discrete=False):
-        if horizon not in ("infinite", "finite", "discrete"):
-            raise ValueError(f"horizon = {horizon!r}: 'infinite', 'finite' or 'discrete'")
+                 horizon="infinite", terminal_weights=None, riccati_steps=5, keep_riccati=False, discrete_steps=5, keep_discrete=False,
+                 affine_steps=5, keep_affine=False):
+        if horizon not in ("infinite", "finite", "discrete", "affine"):
+            raise ValueError(f"horizon = {horizon!r}: 'infinite', 'finite', 'discrete' or 'affine'")
         self.horizon, self.riccati_steps, self.keep_riccati = horizon, int(riccati_steps), bool(keep_riccati)
         self.discrete_steps, self.keep_discrete = int(discrete_steps), bool(keep_discrete)
+        self.affine_steps, self.keep_affine = int(affine_steps), bool(keep_affine)
         self.model = model
         nx, nu = model.state_dim, model.input_dim
         X = np.asarray(X, dtype=np.float64)
@@ -98,11 +104,11 @@ class LQRTracker:
         self.ctx = LqrContext(model.model_id, self.K, self.B, self.foh, device, library)
         self.ctx.set_weights(self.Q, self.R)
         self.Qf = None
-        if horizon in ("finite", "discrete"):
+        if horizon in ("finite", "discrete", "affine"):
             qf = load_lqr_terminal_weights(model) if terminal_weights is None else terminal_weights
             self.Qf = self.Q.copy() if qf is None else np.asarray(qf, dtype=np.float64)
             self.ctx.set_terminal_weights(self.Qf)
-        self._riccati = self._discrete = None
+        self._riccati = self._discrete = self._affine = None
         self.ctx.set_flow_params(si_flow_params(model) if par is None else par)
         self.ctx.set_trajectories(self.X, self.U, self.t)
         self._gains = None
@@ -122,9 +128,11 @@ class LQRTracker:
             return self.computeGainsRiccati()
         if self.horizon == "discrete":
             return self.computeGainsDiscrete()
+        if self.horizon == "affine":
+            return self.computeGainsAffine()
         self.n_ok = self.ctx.compute_gains()
         self._gains = self.ctx.download_gains()
-        self._riccati = self._discrete = None
+        self._riccati = self._discrete = self._affine = None
         return self.n_ok
 
     def computeGainsRiccati(self, steps=None, keep=None):
@@ -134,7 +142,7 @@ class LQRTracker:
         self.n_ok = self.ctx.compute_gains_riccati(steps, keep)
         self._gains = self.ctx.download_gains()
         self._riccati = self.ctx.download_riccati() if keep else None
-        self._discrete = None
+        self._discrete = self._affine = None
         return self.n_ok
 
     def computeGainsDiscrete(self, steps=None, keep=None):
@@ -144,8 +152,26 @@ class LQRTracker:
         self.n_ok = self.ctx.compute_gains_discrete(steps, keep)
         self._gains = self.ctx.download_gains()
         self._discrete = self.ctx.download_discrete() if keep else None
-        self._riccati = None
+        self._riccati = self._affine = None
         return self.n_ok
+
+    def computeGainsAffine(self, steps=None, keep=None):
+        """affine finite-horizon gains and feedforward terms of every trajectory (one sweep of [[P, p], [p', s]] each, on the device); they
+        replace the gains held so far"""
+        steps = self.affine_steps if steps is None else int(steps)
+        keep = self.keep_affine if keep is None else bool(keep)
+        self.n_ok = self.ctx.compute_gains_affine(steps, keep)
+        self._gains = self.ctx.download_gains()
+        self._affine = self.ctx.download_affine(keep)
+        self._riccati = self._discrete = None
+        return self.n_ok
+
+    def affine(self):
+        """dict of ff [B][K][nu] (the feedforward terms k_k) of the last affine sweep and, when kept (keep_affine=True or
+        computeGainsAffine(keep=True)), P [B][K][nx][nx], p [B][K][nx], s [B][K]"""
+        if self._affine is None:
+            raise RuntimeError("no affine sweep held: construct with horizon='affine'")
+        return self._affine
 
     def discrete(self):
         """dict of P [B][K][nx][nx], Phi [B][K-1][nx][nx], Gamma [B][K-1][nx][nu] of the last discrete sweep; needs keep_discrete=True (or
@@ -164,7 +190,7 @@ class LQRTracker:
     def setGains(self, G):
         """user-supplied gains [B][K][nu][nx] instead of the computed ones"""
         self.ctx.set_gains(G)
-        self._riccati = self._discrete = None
+        self._riccati = self._discrete = self._affine = None
         self._gains = dict(gains=np.array(G, dtype=np.float64).reshape(self.B, self.K, self.model.input_dim, self.model.state_dim), status=None, iters=None)
 
     @property
@@ -179,8 +205,9 @@ class LQRTracker:
     def iterations(self):
         return self._gains["iters"]
 
-    def getInput(self, t, x, b=0):
-        """LQRTracker::getInput (LQRTracker.cpp:43-65) of trajectory b, on the host: for spot checks of what the device loop applies"""
+    def getInput(self, t, x, b=0, feedforward=None):
+        """LQRTracker::getInput (LQRTracker.cpp:43-65) of trajectory b, on the host: for spot checks of what the device loop applies.
+        feedforward as in track(): None includes the term k_t exactly when the gains held came from the affine sweep."""
         X, U, G, t_max = self.X[b], self.U[b], self.gains[b], float(self.t[b])
         tc = min(max(float(t), 0.0), t_max)
         dt = t_max / (self.K - 1)
@@ -188,7 +215,17 @@ class LQRTracker:
         i = min(int(tc / dt), self.K - 2)
         j = i + 1 if self.foh else i
         x_ref = X[i] + a * (X[i + 1] - X[i])
-        return -(G[i] + a * (G[j] - G[i])) @ (np.asarray(x, dtype=np.float64) - x_ref) + U[i] + a * (U[j] - U[i])
+        u = -(G[i] + a * (G[j] - G[i])) @ (np.asarray(x, dtype=np.float64) - x_ref) + U[i] + a * (U[j] - U[i])
+        if self._feedforward_on(feedforward):
+            ff = self._affine["ff"][b]
+            u = u - (ff[i] + a * (ff[j] - ff[i]))
+        return u
+
+    def _feedforward_on(self, feedforward):
+        on = (self._affine is not None) if feedforward is None else bool(feedforward)
+        if on and self._affine is None:
+            raise RuntimeError("no feedforward terms held: compute the gains with horizon='affine' (computeGainsAffine)")
+        return on
 
     def setInputLimits(self, lim=None):
         """Input limits inside the closed loop: None (the default) none, "model" the row of the model's parameters (model_input_limits), or
@@ -200,16 +237,20 @@ class LQRTracker:
             lim = model_input_limits(self.model)
         self.ctx.set_input_limits(lim)
 
-    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30, samples=1, hold="step"):
+    def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30, samples=1, hold="step",
+              feedforward=None):
         """The loop of SC_tracking.cpp:48-75 on the device, `samples` flights per trajectory from x_start [B * samples][nx] (flight f follows
         trajectory f // samples; samples = 1: one flight per trajectory).  Returns x, u, t, steps, status, err0, err1 (|x - x_final| at
         start / end), max_dev (largest |x - x_ref|), n_sat (plant steps on which the input limits clipped), max_clip (largest
         |u_cmd - u|; both 0 without limits), n_finite and, with n_record > 0, `record` (of the first n_record flights).
         hold="step" (the default): the feedback term changes on every plant step; hold="node": du = -G[i] (x - x_ref) is latched at the
-        first plant step of segment i and held over it (the loop horizon="discrete" designs for)."""
+        first plant step of segment i and held over it (the loop horizon="discrete" designs for).
+        feedforward: True applies u_cmd = u_ref - K_t (x - x_ref) - k_t with the terms of the affine sweep, False flies without them; None
+        (the default) means on exactly when the gains held came from the affine sweep.  Together with hold="node" it is refused."""
         if hold not in ("step", "node"):
             raise ValueError(f"hold = {hold!r}: 'step' or 'node'")
         self.ctx.set_feedback_hold(1 if hold == "node" else 0)
+        self.ctx.set_feedforward(1 if self._feedforward_on(feedforward) else 0)
         x_final = self.model.p.x_final if x_final is None else x_final
         x_final = np.array(list(x_final), dtype=np.float64)
         if max_steps is None:

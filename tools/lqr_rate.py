@@ -2,7 +2,7 @@
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
     python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--covariance-discrete STEPS]
-                              [--out FILE]
+                              [--affine STEPS] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
 segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
@@ -33,6 +33,12 @@ leg's.  It only ADDS keys (covariance_discrete_*): the sweep's wall time, right-
 stage evaluates the Jacobian twice), the status counts and the final position standard deviation, next to the continuous sweep's under the
 same gains and inputs in the same run (covariance_discrete_continuous_*).
 
+--affine STEPS (measure(affine=STEPS)) adds, after every other leg, the affine finite-horizon sweep (gains and feedforward terms against the
+defect of the solver's trajectories, STEPS RKF78 steps per segment), timed next to the Riccati sweep at the same STEPS IN THE SAME RUN
+(affine_riccati_wall_s: the yardstick of affine_wall_s), then the N flights of the default leg under those gains with the feedforward term and
+without it.  It only ADDS keys (affine_*): the two wall times and their ratio, right-hand sides/s, the status counts, and per flight leg the
+final errors (err1) and the largest excursion (max_dev): nothing of it needs a record.
+
 The flight call of the saturate and samples legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
 best of --repeat.
 """
@@ -50,7 +56,7 @@ import scpp_amd  # noqa: E402
 
 
 def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None,
-            covariance_discrete=None):
+            covariance_discrete=None, affine=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -85,6 +91,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
         ric.update(discrete_leg(trk, x0, int(discrete), repeat))
     if covariance_discrete:
         ric.update(covariance_discrete_leg(trk, int(covariance_discrete), repeat, "discrete" if discrete else "riccati" if riccati else "frozen"))
+    if affine:
+        ric.update(affine_leg(trk, x0, int(affine), repeat))
     trk.close()
     fin = out["status"] != -2
     e = out["err1"][fin]
@@ -191,6 +199,46 @@ def riccati_leg(trk, x0, steps, repeat):
         "riccati_final_error_p5_p50_p95": [float(v) for v in np.percentile(e, [5, 50, 95])] if e.size else [],
         "riccati_max_excursion_p50": float(np.median(out["max_dev"][fin])) if fin.any() else None,
     }
+
+
+def affine_leg(trk, x0, steps, repeat):
+    """the affine sweep on the tracker's trajectories next to the Riccati sweep at the same step count, then the default leg's flights under its
+    gains with and without the feedforward term"""
+    def timed(sweep):
+        sweep(steps)  # warm
+        tc = []
+        for _ in range(repeat):
+            t = time.perf_counter()
+            n_ok = sweep(steps)  # returns after the status of every node is on the host
+            tc.append(time.perf_counter() - t)
+        return min(tc), n_ok
+
+    t_r, ok_r = timed(trk.ctx.compute_gains_riccati)
+    t_a, n_ok = timed(trk.ctx.compute_gains_affine)
+    trk.computeGainsAffine(steps, keep=False)
+    st, it, ff = trk.status, trk.iterations, trk.affine()["ff"]
+    rhs = trk.B * (trk.K - 1) * steps * 13
+    res = {
+        "affine_steps_per_segment": steps, "affine_wall_s": t_a, "affine_riccati_wall_s": t_r, "affine_over_riccati": t_a / t_r,
+        "affine_rhs": int(rhs), "affine_rhs_per_s": rhs / t_a, "affine_nodes": int(st.size), "affine_status_ok": int(n_ok),
+        "affine_riccati_status_ok": int(ok_r), "affine_status_nonfinite": int((st == -2).sum()),
+        "affine_status_other": int(((st != 0) & (st != -2)).sum()),
+        "affine_nonfinite_values": int((~np.isfinite(trk.gains)).sum() + (~np.isfinite(ff)).sum()),
+        "affine_steps_behind_node0": int(it[:, 0].max()),
+        "affine_feedforward_norm_p50_max": [float(v) for v in np.percentile(np.linalg.norm(ff, axis=2).max(axis=1), [50, 100])],
+    }
+    for key, on in (("affine_ff", True), ("affine_noff", False)):
+        out = trk.track(x0, feedforward=on)
+        fin = out["status"] != -2
+        res.update({
+            f"{key}_flights_completed": int((out["status"] == 0).sum()), f"{key}_flights_step_cap": int((out["status"] == 1).sum()),
+            f"{key}_flights_nonfinite": int((out["status"] == -2).sum()),
+            f"{key}_output_nonfinite_values": int(sum((~np.isfinite(out[k])).sum() for k in ("x", "u", "t", "err0", "err1", "max_dev"))),
+            f"{key}_final_error_p5_p50_p95": final_errors(out),
+            f"{key}_max_excursion_p5_p50_p95": [float(v) for v in np.percentile(out["max_dev"][fin], [5, 50, 95])] if fin.any() else [],
+        })
+    trk.ctx.set_feedforward(0)
+    return res
 
 
 def discrete_leg(trk, x0, steps, repeat):
@@ -303,10 +351,12 @@ if __name__ == "__main__":
     ap.add_argument("--samples", default="", help="comma-separated flights per trajectory of the sample-fan legs, e.g. 1,4,16")
     ap.add_argument("--discrete", type=int, default=0, help="RKF78 steps per segment of the sampled-data leg (0: no such leg)")
     ap.add_argument("--covariance-discrete", type=int, default=0, help="RKF78 steps per segment of the held loop's covariance leg (0: no such leg)")
+    ap.add_argument("--affine", type=int, default=0, help="RKF78 steps per segment of the affine leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
-                  samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete, covariance_discrete=a.covariance_discrete)
+                  samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete, covariance_discrete=a.covariance_discrete,
+                  affine=a.affine)
     line = json.dumps(res)
     print(line)
     if a.out:
