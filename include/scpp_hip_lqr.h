@@ -24,6 +24,8 @@
  *       (the discrete Riccati recursion over the segments' transition matrices) scpp_hip_lqr_set_feedback_hold
  *   nothing: the reference has no feedforward for a nominal that misses its nodes             scpp_hip_lqr_compute_gains_affine, _download_affine,
  *       (the Riccati sweep on the state [e; 1])                                scpp_hip_lqr_set_feedforward_terms, _set_feedforward
+ *   nothing: the reference does not predict where its loop's centre goes                      scpp_hip_lqr_propagate_moments, _download_moments
+ *       (the covariance sweep on the state [e; 1])
  *
  * Deviations, all deliberate:
  *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
@@ -104,7 +106,23 @@
  *     k_t interpolated with the indices and the fraction of the gain.  The loop that holds its correction over a segment
  *     (scpp_hip_lqr_set_feedback_hold(1)) has no such term here: its optimal offset is an affine DISCRETE recursion, which is not built, and the
  *     two together are refused.  The covariance sweeps describe the dispersion about the mean, which does not depend on c: they are valid under
- *     either setting; the mean itself is not propagated.
+ *     either setting; they do not propagate the mean itself, scpp_hip_lqr_propagate_moments does:
+ *   - scpp_hip_lqr_propagate_moments is an addition: the mean deviation of the continuous loop next to its covariance.  Everything about the
+ *     reference inside segment i is that of scpp_hip_lqr_propagate_covariance: x, u and K_t interpolated with a and the loop's segment index,
+ *     RKF78 with the plant step's tableau, steps >= 1 steps per segment, stage s of step n at a = (n + c_s) / steps, generated Jacobian rows
+ *     on the full state.  With the loop u = u_ref - K_t e - [k_t]:
+ *         dS/dt = A_cl S + S A_cl' + W          S(0) = sigma0     (the covariance sweep's own equation)
+ *         dm/dt = A_cl m + d(t)                 m(0) = mean0      A_cl = A - B K_t
+ *         d(t)  = c(t) - [B(t) k_t]             c = f(x, u) - (X[i+1] - X[i]) / dt     (the defect of the affine sweep)
+ *     k_t = ff[i] + a (ff[j] - ff[i]) with the gain's indices and fraction.  feedforward == 1 takes k_t from the feedforward terms the context
+ *     holds, computed or supplied; feedforward == 0 means d = c.  Order of the sum: c_r = f_r - xdot_r; bk_r = ((0 - B_r0 k_0) - B_r1 k_1) - ...
+ *     over the inputs in order, each step one fused multiply-add; d_r = c_r + bk_r (bk_r = 0 without the term).  The two equations are ONE
+ *     Lyapunov equation, that of z = [e; 1] with the tile [[S, m], [m', 0]] (nx + 1 <= 15); A_cl enters the products with a zero row and column
+ *     nx, and d is added to the slope of m outside them, so S and everything recorded from it are those of scpp_hip_lqr_propagate_covariance at
+ *     the same step count (the augmentation adds products with exact zeros), and S + m m' is never formed.  Node k records m(t_k) and
+ *     du_mean[k] = -G[k] m(t_k) - [ff[k]], the mean correction on top of u_ref; node 0 records mean0 exactly.  It is a linearisation about the
+ *     nominal, it describes the continuous loop only (the mean of the loop that holds its correction belongs with the affine discrete
+ *     recursion, which is not built), and it knows no input limits.
  *   - input limits (scpp_hip_lqr_set_input_limits) are an addition to the tracking loop, off by default: with limits (T_min, T_max, angle_max)
  *     the loop applies u = sat(u_cmd), u_cmd = -K_t (x - x_ref) + u_ref computed as without them.  A non-finite u_cmd retires the flight with
  *     status -2 before sat.  Thrust-vector models (RocketQuat: u = (T_B, tau_z), sat acts on u[0..2] and u[3] passes through; Lander3dof:
@@ -247,6 +265,20 @@ extern "C"
        be NULL.  SCPP_E_STATE before a sweep, and for cov after a sweep with keep_cov == 0. */
     int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *ctx, double *state_std /* [B][K][nx] */, double *input_cov /* [B][K][nu][nu] */,
                                          double *final_cov /* [B][nx][nx] */, int *status /* [B] */, double *cov /* [B][K][nx][nx], keep_cov only */);
+    /* the covariance sweep of the continuous loop together with the loop's mean (the definition is above): one forward sweep of
+       [[S, m], [m', 0]] per trajectory.  mean0 [rows][nx], rows == 1: one row for every trajectory; NULL: mean0 = 0 (rows is not read).
+       Preconditions, SCPP_E_* answers, inputs (scpp_hip_lqr_set_covariance_inputs), status values and what invalidates the sweep are those of
+       scpp_hip_lqr_propagate_covariance; in addition SCPP_E_ARG for feedforward not 0 or 1, a non-finite mean0, rows neither 1 nor the number
+       of trajectories, and SCPP_E_STATE for feedforward == 1 without feedforward terms.  SCPP_LQR_NONFINITE: a non-finite node, input, flight
+       time, gain or (feedforward == 1) feedforward term (zeros in every output), or a tile or du_mean that turned non-finite in segment k, a
+       non-finite flow map at a finite point included (node k+1 and every later node, the mean and final_cov included, are zeros).  Nothing
+       non-finite is ever written.  The covariance part lands where scpp_hip_lqr_download_covariance reads it, which returns the last sweep of
+       any of the three kinds.  The sweep reads neither the feedforward mode nor the feedback hold and changes neither. */
+    int scpp_hip_lqr_propagate_moments(scpp_hip_lqr_ctx *ctx, int steps, int keep_cov, int feedforward, const double *mean0 /* [rows][nx] or NULL */,
+                                       int rows /* 1 or B */, int *n_ok);
+    /* mean [B][K][nx] = m(t_k), input_mean [B][K][nu] = du_mean[k]; either pointer may be NULL.  SCPP_E_STATE unless the last sweep was
+       scpp_hip_lqr_propagate_moments. */
+    int scpp_hip_lqr_download_moments(scpp_hip_lqr_ctx *ctx, double *mean /* [B][K][nx] */, double *input_mean /* [B][K][nu] */);
     /* regulator mode (LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82): with stop_tol > 0 a loop also ends once |x - x_final| < stop_tol.  The
        caller sets a constant two-node "trajectory" (X = x_final, U = u_eq, t = sim_time) and the one gain of the operating point
        (scpp_hip_lqr_set_gains), so that u = -K (x - x_final) + u_eq; the same two kernels, no third.  0 (the default) switches it off. */

@@ -488,6 +488,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_compute_gains_discrete", "scpp_hip_lqr_download_discrete", "scpp_hip_lqr_set_feedback_hold",
     "scpp_hip_lqr_propagate_covariance_discrete",
     "scpp_hip_lqr_compute_gains_affine", "scpp_hip_lqr_download_affine", "scpp_hip_lqr_set_feedforward_terms", "scpp_hip_lqr_set_feedforward",
+    "scpp_hip_lqr_propagate_moments", "scpp_hip_lqr_download_moments",
 ]
 _lqr_libs = {}
 
@@ -649,6 +650,26 @@ class LqrContext:
         _chk(self.lib.scpp_hip_lqr_propagate_covariance_discrete(self.h, int(steps), int(bool(keep_cov)), C.byref(n)),
              "lqr_propagate_covariance_discrete")
         return int(n.value)
+
+    def propagate_moments(self, steps=5, keep_cov=False, feedforward=False, mean0=None):
+        """the covariance sweep of the continuous loop together with the loop's mean deviation (one sweep of [[S, m], [m', 0]] per
+        trajectory); mean0 [B][nx] or one [nx] for every trajectory (None: 0); feedforward: the drive of the mean includes -B k_t of the
+        feedforward terms held.  The covariance part lands where download_covariance reads it, the mean where download_moments does;
+        returns the number of trajectories with status 0"""
+        rows = 1
+        if mean0 is not None:
+            mean0 = np.ascontiguousarray(mean0, dtype=np.float64).reshape(-1, self.nx)
+            rows = int(mean0.shape[0])
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_propagate_moments(self.h, int(steps), int(bool(keep_cov)), int(feedforward), _p(mean0), rows, C.byref(n)),
+             "lqr_propagate_moments")
+        return int(n.value)
+
+    def download_moments(self):
+        """mean [B][K][nx] = m(t_k) and input_mean [B][K][nu] = -G[k] m(t_k) - [ff[k]] of the last moments sweep"""
+        out = dict(mean=np.zeros((self.B, self.K, self.nx)), input_mean=np.zeros((self.B, self.K, self.nu)))
+        _chk(self.lib.scpp_hip_lqr_download_moments(self.h, _p(out["mean"]), _p(out["input_mean"])), "lqr_download_moments")
+        return out
 
     def download_covariance(self, with_cov=False):
         out = dict(state_std=np.zeros((self.B, self.K, self.nx)), input_cov=np.zeros((self.B, self.K, self.nu, self.nu)),

@@ -7,9 +7,11 @@
 #include "lqr_covariance_kernel.h"
 #include "lqr_discrete_kernel.h"
 #include "lqr_covariance_discrete_kernel.h"
+#include "lqr_moments_launch.h"
 
 #ifdef SCPP_HIP_EMU
 #include "scpp_hip_lqr_affine.cpp" // the emulation is one translation unit (its fiber switch is a global symbol of the emulation header)
+#include "scpp_hip_lqr_moments.cpp"
 #endif
 
 #include <cmath>
@@ -73,6 +75,10 @@ struct scpp_hip_lqr_ctx
     size_t cov_cap = 0;
     int s0_rows = 0; // rows given to scpp_hip_lqr_set_covariance_inputs: 1 (shared) or the number of trajectories
     bool have_cov_in = false, have_cov = false, cov_kept = false;
+    // moments sweep (scpp_hip_lqr_propagate_moments): the covariance part lands in the buffers above; mean0, m(t_k) and du_mean[k] in three of
+    // their own, allocated by the first sweep
+    double *m0 = nullptr, *cmean = nullptr, *cdu = nullptr;
+    bool have_mom = false; // the last sweep was the moments sweep (read together with have_cov, which everything that invalidates a sweep clears)
     double *xs = nullptr, *xf = nullptr, *ox = nullptr, *ou = nullptr, *os = nullptr;
     int *oi = nullptr;
     double *rx = nullptr, *ru = nullptr, *rt = nullptr;
@@ -235,7 +241,7 @@ static int propagateCovariance(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int
         return SCPP_E_STATE; // no gains, no initial covariance, or one for another number of trajectories
     DeviceGuard guard(c->device);
     const size_t need = size_t(c->B) * c->K * c->nx * c->nx;
-    c->have_cov = false;
+    c->have_cov = c->have_mom = false;
     if (keep_cov)
         if (int rc = growTo(c, &c->cov, &c->cov_cap, need))
             return rc;
@@ -350,7 +356,7 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as};
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as, c->m0, c->cmean, c->cdu};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -764,6 +770,57 @@ int scpp_hip_lqr_propagate_covariance(scpp_hip_lqr_ctx *c, int steps, int keep_c
 int scpp_hip_lqr_propagate_covariance_discrete(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok)
 {
     return propagateCovariance(c, steps, keep_cov, n_ok, true);
+}
+
+int scpp_hip_lqr_propagate_moments(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int feedforward, const double *mean0, int rows, int *n_ok)
+{
+    if (!c || steps < 1 || (feedforward != 0 && feedforward != 1))
+        return SCPP_E_ARG;
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (mean0 && ((rows != 1 && rows != c->B) || !allFinite(mean0, size_t(rows) * c->nx)))
+        return SCPP_E_ARG;
+    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B) || (feedforward && !c->have_ff))
+        return SCPP_E_STATE; // as scpp_hip_lqr_propagate_covariance, or a feedforward term asked for that the context does not hold
+    DeviceGuard guard(c->device);
+    const size_t Bm = size_t(c->Bmax), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
+    c->have_cov = c->have_mom = false;
+    if (!c->m0 && (devAlloc(&c->m0, Bm * nx) | devAlloc(&c->cmean, Bm * K * nx) | devAlloc(&c->cdu, Bm * K * nu)))
+        return SCPP_E_HIP;
+    if (keep_cov)
+        if (int rc = growTo(c, &c->cov, &c->cov_cap, size_t(c->B) * K * nx * nx))
+            return rc;
+    if (mean0)
+    {
+        CHECK_HIP(hipMemcpyAsync(c->m0, mean0, size_t(rows) * nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream)); // the host array is the caller's
+    }
+    if (!launchMomentsSweep(c->model, c->stream, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par, c->par_stride, c->G,
+                            c->gains_computed ? c->gstatus : nullptr, c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, c->cw,
+                            feedforward ? c->ff : nullptr, mean0 ? c->m0 : nullptr, rows == 1 ? 0 : c->nx, c->cstd, c->cin, c->cfin, c->cstatus,
+                            keep_cov ? c->cov : nullptr, c->cmean, c->cdu))
+        return SCPP_E_ARG;
+    if (hipGetLastError() != hipSuccess)
+        return SCPP_E_HIP;
+    c->have_cov = c->have_mom = true;
+    c->cov_kept = keep_cov != 0;
+    return countOk(c, c->cstatus, size_t(c->B), n_ok);
+}
+
+int scpp_hip_lqr_download_moments(scpp_hip_lqr_ctx *c, double *mean, double *input_mean)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_cov || !c->have_mom)
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t nodes = size_t(c->B) * c->K;
+    if (mean)
+        CHECK_HIP(hipMemcpyAsync(mean, c->cmean, nodes * c->nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (input_mean)
+        CHECK_HIP(hipMemcpyAsync(input_mean, c->cdu, nodes * c->nu * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
+    return SCPP_OK;
 }
 
 int scpp_hip_lqr_download_covariance(scpp_hip_lqr_ctx *c, double *state_std, double *input_cov, double *final_cov, int *status, double *cov)

@@ -79,6 +79,14 @@ struct lqr_covariance_result_t
     int n_ok = 0;
 };
 
+// the covariance sweep of the continuous loop together with the loop's mean (scpp_hip_lqr_propagate_moments): dm/dt = A_cl m + d, m(0) = mean0,
+// d = c - [B k_t], c the defect of the nominal.  A linearisation about the nominal, of the continuous loop, without input limits.
+struct lqr_moments_result_t : lqr_covariance_result_t
+{
+    std::vector<double> mean;       // [B][K][NX]  m(t_k)
+    std::vector<double> input_mean; // [B][K][NU]  -G[k] m(t_k) - [ff[k]]: the mean correction on top of u_ref
+};
+
 class LQRTracker
 {
 public:
@@ -377,6 +385,42 @@ public:
         check(scpp_hip_lqr_download_covariance(ctx, out.state_std.data(), out.input_cov.data(), out.final_cov.data(), out.status.data(),
                                                o.keep ? out.cov.data() : nullptr),
               "scpp_hip_lqr_download_covariance");
+    }
+
+    // covariance() of the continuous loop (o.hold_node is refused: the held loop's mean is not built) together with the mean deviation, in one
+    // sweep per trajectory.  mean0: empty (0), one [NX] row for every trajectory or [B][NX].  feedforward < 0 (the default): the drive of the
+    // mean includes -B k_t exactly when the tracker holds the terms of an affine sweep; 0 / 1: without / with them.
+    void moments(const lqr_covariance_options_t &o, const std::vector<double> &mean0, lqr_moments_result_t &out, int feedforward = -1)
+    {
+        const size_t B = tds.size(), K = tds[0].n_X();
+        if (o.hold_node)
+            throw std::invalid_argument("LQRTracker::moments: the mean of the loop that holds its correction is not built");
+        if (o.sigma0.size() != NX * NX && o.sigma0.size() != B * NX * NX)
+            throw std::invalid_argument("LQRTracker::moments: sigma0 is one NX x NX matrix, or one per trajectory");
+        if (!o.disturbance.empty() && o.disturbance.size() != NX)
+            throw std::invalid_argument("LQRTracker::moments: disturbance needs one entry per state");
+        if (!mean0.empty() && mean0.size() != NX && mean0.size() != B * NX)
+            throw std::invalid_argument("LQRTracker::moments: mean0 is one row of NX entries, or one per trajectory");
+        const bool ff = feedforward < 0 ? !this->feedforward.empty() : feedforward != 0;
+        if (ff && this->feedforward.empty())
+            throw std::invalid_argument("LQRTracker::moments: no feedforward terms held (lqr_gain_options_t::affine)");
+        check(scpp_hip_lqr_set_covariance_inputs(ctx, o.sigma0.data(), int(o.sigma0.size() / (NX * NX)),
+                                                 o.disturbance.empty() ? nullptr : o.disturbance.data()),
+              "scpp_hip_lqr_set_covariance_inputs");
+        check(scpp_hip_lqr_propagate_moments(ctx, o.steps, o.keep ? 1 : 0, ff ? 1 : 0, mean0.empty() ? nullptr : mean0.data(),
+                                             mean0.empty() ? 1 : int(mean0.size() / NX), &out.n_ok),
+              "scpp_hip_lqr_propagate_moments");
+        out.state_std.assign(B * K * NX, 0.);
+        out.input_cov.assign(B * K * NU * NU, 0.);
+        out.final_cov.assign(B * NX * NX, 0.);
+        out.status.assign(B, 0);
+        out.cov.assign(o.keep ? B * K * NX * NX : 0, 0.);
+        out.mean.assign(B * K * NX, 0.);
+        out.input_mean.assign(B * K * NU, 0.);
+        check(scpp_hip_lqr_download_covariance(ctx, out.state_std.data(), out.input_cov.data(), out.final_cov.data(), out.status.data(),
+                                               o.keep ? out.cov.data() : nullptr),
+              "scpp_hip_lqr_download_covariance");
+        check(scpp_hip_lqr_download_moments(ctx, out.mean.data(), out.input_mean.data()), "scpp_hip_lqr_download_moments");
     }
 
     // the optional vector `name` of LQR.info (initial_std, disturbance_std: one entry per state); empty without the file or the entry

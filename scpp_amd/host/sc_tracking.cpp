@@ -20,6 +20,11 @@
 //   --covariance-hold step|node : which loop --covariance describes.  step (default): the continuous loop; node: the loop that latches its
 //                         correction at each node and holds it over the segment (scpp_hip_lqr_propagate_covariance_discrete), the loop
 //                         --hold node flies.  Used only with --covariance; the same two files
+//   --mean              : also where the loop's centre goes (scpp_hip_lqr_propagate_moments): dm/dt = A_cl m + d from m(0) = 0, d the defect of
+//                         the nominal minus, under --gains affine without --no-feedforward, B k_t.  Used only together with --covariance and
+//                         the continuous loop: with --covariance-hold node it is refused before anything is solved (the held loop's mean is
+//                         not built).  --mean-steps n RKF78 steps per segment (default: those of --covariance-steps).  Writes mean.txt and
+//                         input_mean.txt (one node per row; the mean correction -G m - k on top of u_ref) of instance 0 next to X.txt
 //   --saturate          : input limits inside the closed loop (scpp_hip_lqr_set_input_limits), from the model's parameters T_min, T_max,
 //                         gimbal_max.  Writes n_sat.txt (plant steps on which the input was clipped) and max_clip.txt (largest |u_cmd - u|),
 //                         one flight per row, next to X.txt
@@ -50,8 +55,8 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
-    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false, no_feedforward = false;
-    int covariance_steps = 5, samples = 1;
+    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false, no_feedforward = false, mean = false;
+    int covariance_steps = 5, samples = 1, mean_steps = 0;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
     for (int i = 1; i < argc; i++)
@@ -122,6 +127,10 @@ int main(int argc, char **argv)
             }
             covariance_hold_node = which == "node";
         }
+        else if (!std::strcmp(argv[i], "--mean"))
+            mean = true;
+        else if (!std::strcmp(argv[i], "--mean-steps"))
+            mean_steps = std::atoi(next());
         else if (!std::strcmp(argv[i], "--saturate"))
             saturate = true;
         else if (!std::strcmp(argv[i], "--samples"))
@@ -138,6 +147,16 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
             return 2;
         }
+    }
+    if (mean && !covariance)
+    {
+        std::fprintf(stderr, "--mean: used only together with --covariance\n");
+        return 2;
+    }
+    if (mean && covariance_hold_node)
+    {
+        std::fprintf(stderr, "--mean with --covariance-hold node: the mean of the loop that holds its correction is not built\n");
+        return 2;
     }
     try
     {
@@ -188,6 +207,7 @@ int main(int argc, char **argv)
 
         // closed-loop covariance along every trajectory
         scpp::lqr_covariance_result_t cov;
+        scpp::lqr_moments_result_t mom;
         if (covariance)
         {
             constexpr size_t NX = Model::state_dim;
@@ -209,6 +229,15 @@ int main(int argc, char **argv)
                         rhs, 1e3 * t_cov, cov.n_ok, N);
             if (covariance_hold_node)
                 std::printf("Covariance hold: node (the sweep of the loop that holds its correction over a segment)\n");
+            if (mean)
+            {
+                const bool ff = gain_opts.affine && !no_feedforward;
+                co.steps = mean_steps > 0 ? mean_steps : covariance_steps;
+                t0 = seconds();
+                tracker.moments(co, {}, mom, ff ? 1 : 0);
+                std::printf("Mean: %d RKF78 steps per segment, covariance and mean in %.2f ms, feedforward term %s (%d of %zu trajectories with status 0)\n",
+                            co.steps, 1e3 * (seconds() - t0), ff ? "in" : "not in", mom.n_ok, N);
+            }
         }
 
         // the starts: `samples` per trajectory, the first of each the state its trajectory was solved for
@@ -316,6 +345,20 @@ int main(int argc, char **argv)
             }
             scpp::writeRows(outputPath / "state_std.txt", sd);
             scpp::writeRows(outputPath / "input_cov.txt", ic);
+            if (mean)
+            {
+                // m(t_k) and the mean correction of instance 0, one node per row, round-trip precision
+                std::ofstream fm(outputPath / "mean.txt"), fu(outputPath / "input_mean.txt");
+                fm.precision(17);
+                fu.precision(17);
+                for (size_t k = 0; k < Kn; k++)
+                {
+                    for (size_t j = 0; j < NX; j++)
+                        fm << mom.mean[k * NX + j] << (j + 1 < NX ? ", " : "\n");
+                    for (size_t j = 0; j < NU; j++)
+                        fu << mom.input_mean[k * NU + j] << (j + 1 < NU ? ", " : "\n");
+                }
+            }
         }
         std::printf("output: %s\n", outputPath.string().c_str());
     }

@@ -282,6 +282,20 @@ class LQRTracker:
         out["n_ok"] = n_ok
         return out
 
+    def moments(self, sigma0, disturbance=None, mean0=None, steps=5, keep=False, feedforward=None):
+        """covariance() of the continuous loop together with where the loop's centre goes, in ONE sweep per trajectory on the device:
+        dm/dt = A_cl m + d, m(0) = mean0 ([nx] for every trajectory or [B][nx]; None: 0), d = c - [B k_t], c = f(x_ref, u_ref) - dx_ref/dt the
+        defect of the nominal.  feedforward as in track(): True includes the terms of the affine sweep, False leaves them out, None means on
+        exactly when the gains held came from the affine sweep.  Returns covariance()'s dict (bitwise that of covariance() at the same steps)
+        plus mean [B][K][nx] = m(t_k) and input_mean [B][K][nu] = -G[k] m(t_k) - [ff[k]], the mean correction on top of u_ref.  A
+        linearisation about the nominal, of the continuous loop (hold="step") without input limits; the held loop's mean is not built."""
+        self.ctx.set_covariance_inputs(sigma0, disturbance)
+        n_ok = self.ctx.propagate_moments(steps, keep, self._feedforward_on(feedforward), mean0)
+        out = self.ctx.download_covariance(keep)
+        out.update(self.ctx.download_moments())
+        out["n_ok"] = n_ok
+        return out
+
     def close(self):
         self.ctx.close()
 

@@ -2,6 +2,7 @@
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
     python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--covariance-discrete STEPS]
+                             [--affine STEPS] [--moments STEPS]
                               [--affine STEPS] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
@@ -39,6 +40,14 @@ defect of the solver's trajectories, STEPS RKF78 steps per segment), timed next 
 without it.  It only ADDS keys (affine_*): the two wall times and their ratio, right-hand sides/s, the status counts, and per flight leg the
 final errors (err1) and the largest excursion (max_dev): nothing of it needs a record.
 
+--moments STEPS (measure(moments=STEPS)) adds, last of all, the sweep of the closed-loop mean next to the covariance
+(LQRTracker.moments, STEPS RKF78 steps per segment) under the affine law's gains, which the leg computes itself, timed next to the covariance
+sweep on the same gains and inputs IN THE SAME RUN (moments_covariance_wall_s: the yardstick of moments_wall_s), with the feedforward term
+and without it.  It only ADDS keys (moments_*): the wall times and their ratio, right-hand sides/s, the status counts, and per trajectory
+the split of the final error: |m(T)| with and without the term (where the linearised loop's centre ends relative to the nominal's last
+node), |X[K-1] - x_final| (the nominal's own last node against the target) and the flown |x(T) - X[K-1]| of the default leg's flights under
+the same gains, each as 5 / 50 / 95 % over the trajectories.
+
 The flight call of the saturate and samples legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
 best of --repeat.
 """
@@ -56,7 +65,7 @@ import scpp_amd  # noqa: E402
 
 
 def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None,
-            covariance_discrete=None, affine=None):
+            covariance_discrete=None, affine=None, moments=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -93,6 +102,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
         ric.update(covariance_discrete_leg(trk, int(covariance_discrete), repeat, "discrete" if discrete else "riccati" if riccati else "frozen"))
     if affine:
         ric.update(affine_leg(trk, x0, int(affine), repeat))
+    if moments:
+        ric.update(moments_leg(trk, x0, int(moments), repeat))
     trk.close()
     fin = out["status"] != -2
     e = out["err1"][fin]
@@ -241,6 +252,60 @@ def affine_leg(trk, x0, steps, repeat):
     return res
 
 
+def moments_leg(trk, x0, steps, repeat):
+    """the moments sweep on the tracker's trajectories under the affine law next to the covariance sweep on the same gains and inputs, then the
+    split of the final error: the predicted mean at T, the nominal's last node against the target, and the flown distance to that node"""
+    trk.computeGainsAffine(steps, keep=False)
+    sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
+    trk.ctx.set_covariance_inputs(np.diag(sd * sd), 0.01 * sd * sd)
+
+    def timed(sweep):
+        sweep()  # warm
+        tc = []
+        for _ in range(repeat):
+            t = time.perf_counter()
+            n_ok = sweep()  # returns after the status of every trajectory is on the host
+            tc.append(time.perf_counter() - t)
+        return min(tc), n_ok
+
+    def pct(v):
+        v = v[np.isfinite(v)]
+        return [float(q) for q in np.percentile(v, [5, 50, 95])] if v.size else []
+
+    t_c, ok_c = timed(lambda: trk.ctx.propagate_covariance(steps))
+    cov = trk.ctx.download_covariance()
+    x_final = np.array(list(trk.model.p.x_final), dtype=np.float64)
+    rhs = trk.B * (trk.K - 1) * steps * 13
+    res = {"moments_steps_per_segment": steps, "moments_covariance_wall_s": t_c, "moments_covariance_status_ok": int(ok_c), "moments_rhs": int(rhs),
+           "moments_covariance_rhs_per_s": rhs / t_c, "moments_trajectories": int(trk.B),
+           "moments_nominal_last_node_to_target_p5_p50_p95": pct(np.linalg.norm(trk.X[:, -1] - x_final, axis=1))}
+    for key, on in (("moments_ff", True), ("moments_noff", False)):
+        t_m, n_ok = timed(lambda: trk.ctx.propagate_moments(steps, False, on))
+        o = trk.ctx.download_covariance()
+        o.update(trk.ctx.download_moments())
+        st = o["status"]
+        ok = st != -2
+        fl = trk.track(x0, feedforward=on)
+        fin = ok & (fl["status"] != -2)
+        res.update({
+            f"{key}_wall_s": t_m, f"{key}_over_covariance": t_m / t_c, f"{key}_rhs_per_s": rhs / t_m, f"{key}_status_ok": int(n_ok),
+            f"{key}_status_gains_incomplete": int((st == 2).sum()), f"{key}_status_nonfinite": int((st == -2).sum()),
+            f"{key}_status_other": int(((st != 0) & (st != 2) & (st != -2)).sum()),
+            f"{key}_nonfinite_values": int(sum((~np.isfinite(o[k])).sum() for k in ("state_std", "input_cov", "final_cov", "mean", "input_mean"))),
+            f"{key}_covariance_block_equal": bool(all(np.array_equal(o[k], cov[k]) for k in ("state_std", "input_cov", "final_cov", "status"))),
+            f"{key}_mean_final_norm_p5_p50_p95": pct(np.linalg.norm(o["mean"][ok, -1], axis=1)),
+            f"{key}_mean_final_position_p5_p50_p95": pct(np.linalg.norm(o["mean"][ok, -1, 1:4], axis=1)),  # RocketQuat: states 1..3
+            f"{key}_input_mean_max_norm_p50_max": [float(v) for v in np.percentile(np.linalg.norm(o["input_mean"][ok], axis=2).max(axis=1), [50, 100])] if ok.any() else [],
+            f"{key}_flown_to_last_node_p5_p50_p95": pct(np.linalg.norm(fl["x"][fin] - trk.X[fin, -1], axis=1)),
+            f"{key}_flown_minus_mean_p5_p50_p95": pct(np.linalg.norm(fl["x"][fin] - trk.X[fin, -1] - o["mean"][fin, -1], axis=1)),
+            f"{key}_flown_final_error_p5_p50_p95": pct(fl["err1"][fin]),
+            f"{key}_flights_nonfinite": int((fl["status"] == -2).sum()),
+        })
+    trk.ctx.set_feedforward(0)
+    res["moments_wall_s"], res["moments_over_covariance"] = res["moments_ff_wall_s"], res["moments_ff_over_covariance"]
+    return res
+
+
 def discrete_leg(trk, x0, steps, repeat):
     """sampled-data gains on the tracker's trajectories, then the default leg's flights under them with the feedback term held over a segment"""
     trk.ctx.compute_gains_discrete(steps)  # warm
@@ -352,11 +417,12 @@ if __name__ == "__main__":
     ap.add_argument("--discrete", type=int, default=0, help="RKF78 steps per segment of the sampled-data leg (0: no such leg)")
     ap.add_argument("--covariance-discrete", type=int, default=0, help="RKF78 steps per segment of the held loop's covariance leg (0: no such leg)")
     ap.add_argument("--affine", type=int, default=0, help="RKF78 steps per segment of the affine leg (0: no such leg)")
+    ap.add_argument("--moments", type=int, default=0, help="RKF78 steps per segment of the mean-and-covariance leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
                   samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete, covariance_discrete=a.covariance_discrete,
-                  affine=a.affine)
+                  affine=a.affine, moments=a.moments)
     line = json.dumps(res)
     print(line)
     if a.out:
