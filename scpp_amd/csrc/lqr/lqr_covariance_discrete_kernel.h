@@ -24,10 +24,10 @@
 //
 // Registers, from the compiler's kernel-resource-usage report (hipcc -O3, gfx950).  __launch_bounds__(64, 2), the discrete gain kernel's, holds
 // the compiler to 256 registers per lane.  No scratch and no vector-register spill for any model; scalar values the compiler parks in lanes of
-// a vector register (its "SGPRs Spill": 104 / 134 / 106 below, 88 / 94 / 89 in the discrete gain kernel) never touch memory.
+// a vector register (its "SGPRs Spill": 103 / 123 / 105 below, 99 / 107 / 99 in the discrete gain kernel) never touch memory.
 //                   VGPR   AGPR   scratch bytes/lane   wavefronts per SIMD   LDS bytes
-//     Lander3dof     171      0                    0                     2        6080
-//     Rocket2D       202      0                    0                     2        6080
+//     Lander3dof     170      0                    0                     2        6080
+//     Rocket2D       200      0                    0                     2        6080
 //     RocketQuat     229      0                    0                     2        6080
 #pragma once
 #include "lqr_covariance_kernel.h"
@@ -60,38 +60,22 @@ __global__ void __launch_bounds__(WAVE, COVARIANCE_DISCRETE_WAVES_PER_SIMD)
     const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
     const long b = blockIdx.x;
     const bool foh = (nU == K);
-    const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU, *Gb = G + b * K * NU * NX;
-    double *sdb = sd + b * K * NX, *icb = icov + b * K * NU * NU, *fcb = fcov + b * NX * NX;
-    double *cvb = cov ? cov + b * K * NX * NX : nullptr;
+    const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU;
+    const ForwardIo io = forwardIo<NX, NU>(b, K, G, nullptr, sd, icov, fcov, cov, nullptr, nullptr);
 
     for (int e = lane; e < RT * RT; e += WAVE)
         lds.At[e] = 0.;
     lds.Bm[lane] = 0.;
     double p[NP], aux[JR::NAUX > 0 ? JR::NAUX : 1];
-    for (int j = 0; j < NP; j++)
-        p[j] = par[b * par_stride + j];
-    JR::prepare(p, aux);
+    loadParameters<P>(par, b, par_stride, p, aux);
     const d4_t wd = diagonalTile<NX>(lane, w);
     bool noise = false; // wave-uniform: every lane reads all of w
     for (int j = 0; j < NX; j++)
         noise = noise || w[j] != 0.;
-    d4_t Sc;
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-    {
-        const int row = 4 * r + g;
-        const bool in = row < NX && col < NX;
-        Sc[r] = in ? S0[b * s0_stride + (in ? row * NX + col : 0)] : 0.;
-    }
+    int bad = 0, incomplete;
+    d4_t Sc = loadInitialTile<NX, false>(lane, S0 + b * s0_stride, nullptr, bad);
     const double t_max = T[b];
-    int bad = referenceNonFinite<NX, NU>(lane, t_max, Xb, Ub, K, nU), incomplete = 0;
-    for (int e = lane; e < K * NU * NX; e += WAVE)
-        bad |= isFinite(Gb[e]) ? 0 : 1;
-    if (gstatus)
-        for (int e = lane; e < K; e += WAVE)
-            incomplete |= gstatus[b * K + e] != ST_OK ? 1 : 0;
-    bad = waveOr(bad);
-    incomplete = waveOr(incomplete);
+    scanForwardInputs<NX, NU, false>(lane, t_max, Xb, Ub, K, nU, io, gstatus ? gstatus + b * K : nullptr, bad, incomplete);
     WAVE_SYNC();
 
     const double h = t_max / double(K - 1) / double(steps);
@@ -157,7 +141,7 @@ __global__ void __launch_bounds__(WAVE, COVARIANCE_DISCRETE_WAVES_PER_SIMD)
             }
             // ---- one step of the recursion: S_i -> S_k = Acl S_i Acl' + Wd ----
             const bool inG = g < NU && col < NX;
-            const double gg = inG ? Gb[(i * NU + (inG ? g : 0)) * NX + (inG ? col : 0)] : 0.;
+            const double gg = inG ? io.Gb[(i * NU + (inG ? g : 0)) * NX + (inG ? col : 0)] : 0.;
             d4_t AclT = {0., 0., 0., 0.};
             AclT = __builtin_amdgcn_mfma_f64_16x16x4f64(gg, ga, AclT, 0, 0, 0); // (Gamma G)': register r of lane l is (Gamma G)[col][4r + g]
 #pragma unroll
@@ -174,47 +158,13 @@ __global__ void __launch_bounds__(WAVE, COVARIANCE_DISCRETE_WAVES_PER_SIMD)
                 Sc[r] = 0.5 * (F[r] + lds.M[col * RT + 4 * r + g]) + Md[r];
             WAVE_SYNC();
         }
-        // ---- node k: S_k, its standard deviations and the input covariance G[k] S G[k]' = G (S G')  (8 matrix-core instructions) ----
-        double Gt[4]; // the lane's share of the gain tile (rows >= nu zero): G[col][4c + g]
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-        {
-            const bool in = col < NU && 4 * c + g < NX;
-            Gt[c] = in ? Gb[(k * NU + (in ? col : 0)) * NX + (in ? 4 * c + g : 0)] : 0.;
-        }
-        d4_t Wp = {0., 0., 0., 0.}, Sk = {0., 0., 0., 0.};
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-            Wp = __builtin_amdgcn_mfma_f64_16x16x4f64(Sc[c], Gt[c], Wp, 0, 0, 0); // S G': register r of lane l is (S G')[4r + g][col]
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-            Sk = __builtin_amdgcn_mfma_f64_16x16x4f64(Gt[c], Wp[c], Sk, 0, 0, 0); // register 0 of lane l is (G S G')[g][col]
-        if (waveOr((isFinite(Sk[0]) ? 0 : 1) | tileNonFinite(Sc)))
+        if (!forwardNode<NX, NU, false>(lane, k, Sc, io))
         {
             kfail = k;
             break;
         }
-        if (cvb)
-            storeTile<NX>(lane, cvb + k * NX * NX, Sc);
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            if (4 * r + g == col && col < NX)
-                sdb[k * NX + col] = sqrt(Sc[r] > 0. ? Sc[r] : 0.); // a diagonal entry negative from rounding: 0
-        if (g < NU && col < NU)
-            icb[(k * NU + g) * NU + col] = Sk[0];
     }
-    // nothing non-finite is ever written: zeros for the node something went non-finite at and every later one (every node of a non-finite trajectory)
-    for (int e = kfail * NX + lane; e < K * NX; e += WAVE)
-        sdb[e] = 0.;
-    for (int e = kfail * NU * NU + lane; e < K * NU * NU; e += WAVE)
-        icb[e] = 0.;
-    if (cvb)
-        for (int e = kfail * NX * NX + lane; e < K * NX * NX; e += WAVE)
-            cvb[e] = 0.;
-    const d4_t zero = {0., 0., 0., 0.};
-    storeTile<NX>(lane, fcb, kfail == K ? Sc : zero);
-    if (lane == 0)
-        status[b] = kfail < K ? ST_NONFINITE : (incomplete ? ST_GAINS_INCOMPLETE : ST_OK);
+    forwardEpilogue<NX, NU, false>(lane, K, kfail, incomplete, Sc, io, status + b);
 }
 
 } // namespace lqr

@@ -12,15 +12,16 @@
 //     M2 = S A_cl'    4   (A operand: S, B operand: A_cl)     M2[i][j] is bitwise M1[j][i]: the same products, summed in the same order
 //     F  = (M1 + M2) + W
 // S STAYS SYMMETRIC BY CONSTRUCTION (bitwise); nothing is symmetrised.
+//
+// The moments sweep (lqr_moments_kernel.h has its equations) is THE SAME BODY, covarianceSweep<P, MEAN = true>: the tile is [[S, m], [m', 0]],
+// and what the mean adds stands under `if constexpr (MEAN)`.  Its entry point is compiled in a translation unit of its own (lqr_sweep_launch.h).
 #pragma once
-#include "lqr_tile_sweep.h"
+#include "lqr_sweep_frame.h"
 
 namespace scpp
 {
 namespace lqr
 {
-
-constexpr int ST_GAINS_INCOMPLETE = 2;
 
 struct CovarianceLds
 {
@@ -28,6 +29,16 @@ struct CovarianceLds
     double G0[4 * RT], G1[4 * RT]; // gains of the segment's two nodes, [a][c]
     SegmentLds seg;
 };
+
+struct MomentsLds
+{
+    CovarianceLds cov;
+    double dc[RT], db[RT]; // c and -B k_t of the stage, rows >= nx zero
+    double f0[4], f1[4];   // feedforward terms of the segment's two nodes (the gain's indices)
+};
+
+__device__ __forceinline__ CovarianceLds &covarianceLds(CovarianceLds &lds) { return lds; }
+__device__ __forceinline__ CovarianceLds &covarianceLds(MomentsLds &lds) { return lds.cov; }
 
 // F = (A_cl S + S A_cl') + W in the accumulator layout; Ac = the lane's share of the transposed A_cl tile, wd = its share of W
 __device__ __forceinline__ d4_t covarianceRhs(const d4_t Sn, const double (&Ac)[4], const d4_t wd)
@@ -74,11 +85,139 @@ __device__ __forceinline__ void closedLoopJacobian(CovarianceLds &lds, int lane,
     WAVE_SYNC();
 }
 
+// the drive of the mean at the reference's point a of the segment -> LDS: lane NX writes c = f(x, u) - xdot (xdot [NX]: the slope of the reference
+// over the segment, read by lane NX only), lanes r < NX write -B_r k_t = ((0 - B_r0 k_0) - B_r1 k_1) - ..., k_t = f0 + a (f1 - f0) (ff only; zero
+// otherwise).  The caller synchronises before it reads.
+template <class P>
+__device__ __forceinline__ void momentsDrive(MomentsLds &lds, int lane, double a, const double *p, const double *aux, const double *xdot, bool ff)
+{
+    constexpr int NX = P::Model::NX, NU = P::Model::NU;
+    if (lane == NX)
+    {
+        double x[NX], u[NU], f[NX];
+        interpolateSegment(lds.cov.seg, a, x, u);
+        P::Model::template systemFlowMap<double>(x, u, p, f);
+#pragma unroll
+        for (int j = 0; j < NX; j++)
+            lds.dc[j] = f[j] - xdot[j];
+    }
+    else if (lane < NX && ff)
+    {
+        double x[NX], u[NU], jr[NX + NU];
+        interpolateSegment(lds.cov.seg, a, x, u);
+        jacobianRow<P>(lane, x, u, p, aux, jr);
+        double acc = 0.;
+#pragma unroll
+        for (int q = 0; q < NU; q++)
+            acc -= jr[NX + q] * (lds.f0[q] + a * (lds.f1[q] - lds.f0[q]));
+        lds.db[lane] = acc;
+    }
+}
+
 // One sweep per trajectory.  X [B][K][nx], U [B][uRows][nu] (nU rows used), T [B], par [B][np], G [B][K][nu][nx], gstatus [B][K] (nullptr: gains
 // without a status), S0 [B][nx][nx] (s0_stride 0: one matrix for every trajectory), w [nx]  ->  sd [B][K][nx] = sqrt(diag S(t_k)),
 // icov [B][K][nu][nu] = G[k] S(t_k) G[k]', fcov [B][nx][nx] = S(T), status [B], cov [B][K][nx][nx] (nullptr: not kept).
+// MEAN: and FF [B][K][nu] (nullptr: no feedforward term, d = c), M0 [B][nx] (nullptr: mean0 = 0; m0_stride 0: one row for every trajectory)
+// ->  mean [B][K][nx] = m(t_k), dumean [B][K][nu] = -G[k] m(t_k) - [FF[k]]; m is in the tile, so the frame's finiteness check covers it (a
+// non-finite flow map at a finite point fails the node it reaches and every later one).  Lds: CovarianceLds, or MomentsLds with MEAN.
 // Segment i (nodes i, i+1) is integrated from a = 0 up to a = 1 with x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]),
 // K_t = G[i] + a (G[j] - G[i]), j = i+1 (first-order) or i (zero-order); the segment index is the loop's, never derived from a time.
+template <class P, bool MEAN, class Lds>
+__device__ __forceinline__ void covarianceSweep(Lds &mlds, int K, int nU, int uRows, int steps, const double *__restrict__ X, const double *__restrict__ U,
+                                                const double *__restrict__ T, const double *__restrict__ par, int par_stride,
+                                                const double *__restrict__ G, const int *__restrict__ gstatus, const double *__restrict__ S0,
+                                                int s0_stride, const double *__restrict__ w, const double *__restrict__ FF,
+                                                const double *__restrict__ M0, int m0_stride, double *__restrict__ sd, double *__restrict__ icov,
+                                                double *__restrict__ fcov, int *__restrict__ status, double *__restrict__ cov,
+                                                double *__restrict__ mean, double *__restrict__ dumean)
+{
+    using Model = typename P::Model;
+    using JR = typename Model::JacobianRows;
+    constexpr int NX = Model::NX, NU = Model::NU, NP = Model::NP;
+    static_assert(NX + (MEAN ? 1 : 0) <= RT && NU <= 4, "S, or [[S, m], [m', 0]], is one 16 x 16 tile, the gain one 4-row chunk");
+    CovarianceLds &lds = covarianceLds(mlds);
+    const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
+    const long b = blockIdx.x;
+    const bool foh = (nU == K), ff = MEAN && FF != nullptr;
+    const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU;
+    const ForwardIo io = forwardIo<NX, NU>(b, K, G, FF, sd, icov, fcov, cov, mean, dumean);
+
+    for (int e = lane; e < RT * RT; e += WAVE)
+        lds.At[e] = 0.;
+    if constexpr (MEAN)
+        if (lane < RT)
+            mlds.dc[lane] = mlds.db[lane] = 0.;
+    double p[NP], aux[JR::NAUX > 0 ? JR::NAUX : 1];
+    loadParameters<P>(par, b, par_stride, p, aux);
+    const d4_t wd = diagonalTile<NX>(lane, w);
+    int bad = 0, incomplete;
+    d4_t Tc = loadInitialTile<NX, MEAN>(lane, S0 + b * s0_stride, (MEAN && M0) ? M0 + b * m0_stride : nullptr, bad);
+    const double t_max = T[b];
+    scanForwardInputs<NX, NU, MEAN>(lane, t_max, Xb, Ub, K, nU, io, gstatus ? gstatus + b * K : nullptr, bad, incomplete);
+    WAVE_SYNC();
+
+    const double dt = t_max / double(K - 1);
+    const double h = dt / double(steps);
+    int kfail = bad ? 0 : K; // nodes kfail..K-1 carry zeros
+    for (int k = 0; k < K && kfail == K; k++)
+    {
+        if (k > 0)
+        {
+            // ---- segment i = k-1: T(t_i) -> T(t_k), `steps` RKF78 steps ----
+            const int i = k - 1, ju = foh ? k : i;
+            loadSegment<NX, NU>(lds.seg, lane, Xb, Ub, i, ju);
+            if (g < NU && col < NX)
+            {
+                lds.G0[g * RT + col] = io.Gb[(i * NU + g) * NX + col];
+                lds.G1[g * RT + col] = io.Gb[(ju * NU + g) * NX + col];
+            }
+            if constexpr (MEAN)
+                if (ff && lane < NU)
+                {
+                    mlds.f0[lane] = io.Fb[i * NU + lane];
+                    mlds.f1[lane] = io.Fb[ju * NU + lane];
+                }
+            WAVE_SYNC();
+            [[maybe_unused]] double xdot[NX];
+            if constexpr (MEAN)
+                if (lane == NX)
+                {
+#pragma unroll
+                    for (int j = 0; j < NX; j++)
+                        xdot[j] = (lds.seg.x1[j] - lds.seg.x0[j]) / dt;
+                }
+            for (int n = 0; n < steps; n++)
+                rkf78TileStep(Tc, h, [&](int s, const d4_t Ts) __attribute__((always_inline)) {
+                    const double a = (double(n) + RK_C[s]) / double(steps);
+                    double Ac[4];
+                    if constexpr (MEAN)
+                        momentsDrive<P>(mlds, lane, a, p, aux, xdot, ff);
+                    closedLoopJacobian<P>(lds, lane, a, p, aux, Ac); // synchronises after its writes and after its reads
+                    d4_t F = covarianceRhs(Ts, Ac, wd);
+                    if constexpr (MEAN)
+                    {
+                        // d = c + (-B k_t) enters OUTSIDE the products: column NX and row NX add it from the same LDS value
+#pragma unroll
+                        for (int r = 0; r < 4; r++)
+                        {
+                            const int mi = meanIndex<NX>(4 * r + g, col);
+                            if (mi >= 0)
+                                F[r] += mlds.dc[mi] + mlds.db[mi];
+                        }
+                        WAVE_SYNC(); // the next stage writes dc and db
+                    }
+                    return F;
+                });
+        }
+        if (!forwardNode<NX, NU, MEAN>(lane, k, Tc, io))
+        {
+            kfail = k;
+            break;
+        }
+    }
+    forwardEpilogue<NX, NU, MEAN>(lane, K, kfail, incomplete, Tc, io, status + b);
+}
+
 template <class P>
 __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int uRows, int steps, const double *__restrict__ X, const double *__restrict__ U,
                                                                const double *__restrict__ T, const double *__restrict__ par, int par_stride,
@@ -87,112 +226,9 @@ __global__ void __launch_bounds__(WAVE) lqr_covariance_kernel(int K, int nU, int
                                                                double *__restrict__ sd, double *__restrict__ icov, double *__restrict__ fcov,
                                                                int *__restrict__ status, double *__restrict__ cov)
 {
-    using Model = typename P::Model;
-    using JR = typename Model::JacobianRows;
-    constexpr int NX = Model::NX, NU = Model::NU, NP = Model::NP;
-    static_assert(NX <= RT && NU <= 4, "S is one 16 x 16 tile, the gain one 4-row chunk");
     __shared__ CovarianceLds lds;
-    const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
-    const long b = blockIdx.x;
-    const bool foh = (nU == K);
-    const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU, *Gb = G + b * K * NU * NX;
-    double *sdb = sd + b * K * NX, *icb = icov + b * K * NU * NU, *fcb = fcov + b * NX * NX;
-    double *cvb = cov ? cov + b * K * NX * NX : nullptr;
-
-    for (int e = lane; e < RT * RT; e += WAVE)
-        lds.At[e] = 0.;
-    double p[NP], aux[JR::NAUX > 0 ? JR::NAUX : 1];
-    for (int j = 0; j < NP; j++)
-        p[j] = par[b * par_stride + j];
-    JR::prepare(p, aux);
-    const d4_t wd = diagonalTile<NX>(lane, w);
-    d4_t Sc;
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-    {
-        const int row = 4 * r + g;
-        const bool in = row < NX && col < NX;
-        Sc[r] = in ? S0[b * s0_stride + (in ? row * NX + col : 0)] : 0.;
-    }
-    const double t_max = T[b];
-    int bad = referenceNonFinite<NX, NU>(lane, t_max, Xb, Ub, K, nU), incomplete = 0;
-    for (int e = lane; e < K * NU * NX; e += WAVE)
-        bad |= isFinite(Gb[e]) ? 0 : 1;
-    if (gstatus)
-        for (int e = lane; e < K; e += WAVE)
-            incomplete |= gstatus[b * K + e] != ST_OK ? 1 : 0;
-    bad = waveOr(bad);
-    incomplete = waveOr(incomplete);
-    WAVE_SYNC();
-
-    const double h = t_max / double(K - 1) / double(steps);
-    int kfail = bad ? 0 : K; // nodes kfail..K-1 carry zeros
-    for (int k = 0; k < K && kfail == K; k++)
-    {
-        if (k > 0)
-        {
-            // ---- segment i = k-1: S(t_i) -> S(t_k), `steps` RKF78 steps ----
-            const int i = k - 1, ju = foh ? k : i;
-            loadSegment<NX, NU>(lds.seg, lane, Xb, Ub, i, ju);
-            if (g < NU && col < NX)
-            {
-                lds.G0[g * RT + col] = Gb[(i * NU + g) * NX + col];
-                lds.G1[g * RT + col] = Gb[(ju * NU + g) * NX + col];
-            }
-            WAVE_SYNC();
-            for (int n = 0; n < steps; n++)
-                rkf78TileStep(Sc, h, [&](int s, const d4_t Ss) __attribute__((always_inline)) {
-                    const double a = (double(n) + RK_C[s]) / double(steps);
-                    double Ac[4];
-                    closedLoopJacobian<P>(lds, lane, a, p, aux, Ac);
-                    return covarianceRhs(Ss, Ac, wd);
-                });
-        }
-        // ---- node k: S(t_k), its standard deviations and the input covariance G[k] S G[k]' = G (S G')  (8 matrix-core instructions) ----
-        double Gt[4]; // the lane's share of the gain tile (rows >= nu zero): G[col][4c + g]
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-        {
-            const bool in = col < NU && 4 * c + g < NX;
-            Gt[c] = in ? Gb[(k * NU + (in ? col : 0)) * NX + (in ? 4 * c + g : 0)] : 0.;
-        }
-        d4_t Wp = {0., 0., 0., 0.}, Sk = {0., 0., 0., 0.};
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-            Wp = __builtin_amdgcn_mfma_f64_16x16x4f64(Sc[c], Gt[c], Wp, 0, 0, 0); // S G': register r of lane l is (S G')[4r + g][col]
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-            Sk = __builtin_amdgcn_mfma_f64_16x16x4f64(Gt[c], Wp[c], Sk, 0, 0, 0); // register 0 of lane l is (G S G')[g][col]
-        int nf = isFinite(Sk[0]) ? 0 : 1;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            nf |= isFinite(Sc[r]) ? 0 : 1;
-        if (waveOr(nf))
-        {
-            kfail = k;
-            break;
-        }
-        if (cvb)
-            storeTile<NX>(lane, cvb + k * NX * NX, Sc);
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            if (4 * r + g == col && col < NX)
-                sdb[k * NX + col] = sqrt(Sc[r] > 0. ? Sc[r] : 0.); // a diagonal entry negative from rounding: 0
-        if (g < NU && col < NU)
-            icb[(k * NU + g) * NU + col] = Sk[0];
-    }
-    // nothing non-finite is ever written: zeros for the node S went non-finite at and every later one (every node of a non-finite trajectory)
-    for (int e = kfail * NX + lane; e < K * NX; e += WAVE)
-        sdb[e] = 0.;
-    for (int e = kfail * NU * NU + lane; e < K * NU * NU; e += WAVE)
-        icb[e] = 0.;
-    if (cvb)
-        for (int e = kfail * NX * NX + lane; e < K * NX * NX; e += WAVE)
-            cvb[e] = 0.;
-    const d4_t zero = {0., 0., 0., 0.};
-    storeTile<NX>(lane, fcb, kfail == K ? Sc : zero);
-    if (lane == 0)
-        status[b] = kfail < K ? ST_NONFINITE : (incomplete ? ST_GAINS_INCOMPLETE : ST_OK);
+    covarianceSweep<P, false>(lds, K, nU, uRows, steps, X, U, T, par, par_stride, G, gstatus, S0, s0_stride, w, nullptr, nullptr, 0, sd, icov, fcov,
+                              status, cov, nullptr, nullptr);
 }
 
 } // namespace lqr

@@ -19,7 +19,7 @@
 // both sides of the diagonal.  Q dt and Y'Y are symmetric to the bit, so P is, at every node.
 // The nu x nu Cholesky factor and the two triangular solves are scalar work every lane does for its own column.
 #pragma once
-#include "lqr_tile_sweep.h"
+#include "lqr_sweep_frame.h"
 
 namespace scpp
 {
@@ -237,9 +237,7 @@ __global__ void __launch_bounds__(WAVE, DISCRETE_WAVES_PER_SIMD) lqr_discrete_ke
     lds.Bm[lane] = 0.;
     lds.N[lane] = 0.;
     double p[NP], aux[JR::NAUX > 0 ? JR::NAUX : 1];
-    for (int j = 0; j < NP; j++)
-        p[j] = par[b * par_stride + j];
-    JR::prepare(p, aux);
+    loadParameters<P>(par, b, par_stride, p, aux);
     const double t_max = T[b];
     const double dt = t_max / double(K - 1);
     const double h = t_max / double(K - 1) / double(steps);
@@ -378,11 +376,7 @@ __global__ void __launch_bounds__(WAVE, DISCRETE_WAVES_PER_SIMD) lqr_discrete_ke
                 Gb[((K - 1) * NU + g) * NX + col] = gain;
             if (Pb)
                 storeTile<NX>(lane, Pb + (K - 1) * NX * NX, Pc);
-            if (lane == 0)
-            {
-                status[b * K + K - 1] = ST_OK;
-                iters[b * K + K - 1] = 0;
-            }
+            markNodeOk(lane, status + b * K, iters + b * K, K - 1, 0);
         }
         Pc = Pn;
         if (g < NU && col < NX)
@@ -393,29 +387,17 @@ __global__ void __launch_bounds__(WAVE, DISCRETE_WAVES_PER_SIMD) lqr_discrete_ke
             storeTile<NX>(lane, Fb + k * NX * NX, Ph);
             storeInputTile<NX, NU>(lane, Cb + k * NX * NU, Gm);
         }
-        if (lane == 0)
-        {
-            status[b * K + k] = ST_OK;
-            iters[b * K + k] = (K - 1 - k) * steps;
-        }
+        markNodeOk(lane, status + b * K, iters + b * K, k, (K - 1 - k) * steps);
     }
     // a failed node never writes a non-finite value: zeros and its status, for the node of the segment that failed and every earlier one
-    for (int e = lane; e < (kfail + 1) * NU * NX; e += WAVE)
-        Gb[e] = 0.;
+    backwardEpilogue<NX, NU>(lane, kfail, Gb, Pb, status + b * K, iters + b * K);
     if (Pb)
     {
         const int segs = kfail + 1 < K - 1 ? kfail + 1 : K - 1;
-        for (int e = lane; e < (kfail + 1) * NX * NX; e += WAVE)
-            Pb[e] = 0.;
         for (int e = lane; e < segs * NX * NX; e += WAVE)
             Fb[e] = 0.;
         for (int e = lane; e < segs * NX * NU; e += WAVE)
             Cb[e] = 0.;
-    }
-    for (int e = lane; e <= kfail; e += WAVE)
-    {
-        status[b * K + e] = ST_NONFINITE;
-        iters[b * K + e] = 0;
     }
 }
 

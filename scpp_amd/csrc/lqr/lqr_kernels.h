@@ -114,6 +114,17 @@ struct LqrPluginList
 {
 };
 using LqrPlugins = LqrPluginList<RocketQuatLqr, Rocket2dLqr, Lander3dofLqr>;
+// f(Plugin{}) for the plugin whose ID is `model`; false for an id nobody registered
+template <class F, class... PL>
+inline bool withLqrPluginOf(LqrPluginList<PL...>, int model, F &&f)
+{
+    return ((model == PL::ID ? (f(PL{}), true) : false) || ...);
+}
+template <class F>
+inline bool withLqrPlugin(int model, F &&f)
+{
+    return withLqrPluginOf(LqrPlugins{}, model, f);
+}
 
 __device__ __forceinline__ bool isFinite(double v) { return fabs(v) <= 1.7976931348623157e308; } // false for a NaN
 

@@ -13,8 +13,11 @@
 //     F  = (M1 + M2) - S + Q
 // P STAYS SYMMETRIC BY CONSTRUCTION (bitwise: F[i][j] and F[j][i] are the same operations on the same numbers); nothing is symmetrised.
 // The Jacobian rows are the generated rows the gain kernel evaluates: lane r < nx evaluates row r at the interpolated reference and writes it to LDS.
+//
+// The affine sweep (lqr_affine_kernel.h has its equations) is THE SAME BODY, riccatiSweep<P, AFFINE = true>, on the tile [[P, p], [p', s]]; what
+// it adds stands under `if constexpr (AFFINE)`.  Its entry point is compiled in a translation unit of its own (lqr_sweep_launch.h).
 #pragma once
-#include "lqr_tile_sweep.h"
+#include "lqr_sweep_frame.h"
 
 namespace scpp
 {
@@ -80,36 +83,56 @@ __device__ __forceinline__ d4_t riccatiRhs(const d4_t Pn, const double (&At)[4],
     return F;
 }
 
+// riccatiJacobian with the defect column: lane NX writes c = f(x, u) - xdot into column NX of the A tile (rows < NX) before the tiles are read back;
+// xdot [NX] is the slope of the reference over the segment (read by lane NX only)
+template <class P>
+__device__ __forceinline__ void affineJacobian(RiccatiLds &lds, int lane, const double *x, const double *u, const double *p, const double *aux,
+                                               const double *xdot, double (&At)[4], double (&Bt)[4])
+{
+    constexpr int NX = P::Model::NX;
+    if (lane == NX)
+    {
+        double f[NX];
+        P::Model::template systemFlowMap<double>(x, u, p, f);
+#pragma unroll
+        for (int j = 0; j < NX; j++)
+            lds.A[j * RT + NX] = f[j] - xdot[j];
+    }
+    riccatiJacobian<P>(lds, lane, x, u, p, aux, At, Bt);
+}
+
 // One sweep per trajectory.  X [B][K][nx], U [B][uRows][nu] (nU rows used: K first-order hold, K-1 zero-order hold), T [B], par [B][np], q / qf [nx],
 // r [nu]  ->  G [B][K][nu][nx], status [B][K], iters [B][K] = RKF78 steps behind the node, Pout [B][K][nx][nx] (nullptr: not kept).
+// AFFINE: and  ->  FF [B][K][nu] = k_k, pout [B][K][nx], sout [B][K] (the two nullptr: not kept); p and s are in the tile, so the finiteness
+// check covers them (a non-finite flow map of a finite node fails the node it reaches and every earlier one).
 // Segment i (nodes i, i+1) is integrated from a = 1 down to a = 0 with the reference x = X[i] + a (X[i+1] - X[i]), u = U[i] + a (U[j] - U[i]),
 // j = i+1 (first-order) or i (zero-order); the segment index is the loop's, never derived from a time.
-template <class P>
-__global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uRows, int steps, const double *__restrict__ X, const double *__restrict__ U,
-                                                            const double *__restrict__ T, const double *__restrict__ par, int par_stride,
-                                                            const double *__restrict__ qw, const double *__restrict__ rw, const double *__restrict__ qfw,
-                                                            double *__restrict__ G, int *__restrict__ status, int *__restrict__ iters,
-                                                            double *__restrict__ Pout)
+template <class P, bool AFFINE>
+__device__ __forceinline__ void riccatiSweep(RiccatiLds &lds, int K, int nU, int uRows, int steps, const double *__restrict__ X,
+                                             const double *__restrict__ U, const double *__restrict__ T, const double *__restrict__ par, int par_stride,
+                                             const double *__restrict__ qw, const double *__restrict__ rw, const double *__restrict__ qfw,
+                                             double *__restrict__ G, int *__restrict__ status, int *__restrict__ iters, double *__restrict__ FF,
+                                             double *__restrict__ Pout, double *__restrict__ pout, double *__restrict__ sout)
 {
     using Model = typename P::Model;
     using JR = typename Model::JacobianRows;
     constexpr int NX = Model::NX, NU = Model::NU, NP = Model::NP;
-    static_assert(NX <= RT && NU <= 4, "P is one 16 x 16 tile, B'P one 4-row chunk");
-    __shared__ RiccatiLds lds;
+    static_assert(NX + (AFFINE ? 1 : 0) <= RT && NU <= 4, "P, or [[P, p], [p', s]], is one 16 x 16 tile, B'P one 4-row chunk");
     const int lane = threadIdx.x & 63, g = lane >> 4, col = lane & 15;
     const long b = blockIdx.x;
     const bool foh = (nU == K);
     const double *Xb = X + b * K * NX, *Ub = U + b * uRows * NU;
     double *Gb = G + b * K * NU * NX;
     double *Pb = Pout ? Pout + b * K * NX * NX : nullptr;
+    [[maybe_unused]] double *Fb = AFFINE ? FF + b * K * NU : nullptr;
+    [[maybe_unused]] double *pb = (AFFINE && pout) ? pout + b * K * NX : nullptr;
+    [[maybe_unused]] double *sb = (AFFINE && sout) ? sout + b * K : nullptr;
 
     for (int e = lane; e < RT * RT; e += WAVE)
         lds.A[e] = 0.;
     lds.Bm[lane] = 0.;
     double p[NP], aux[JR::NAUX > 0 ? JR::NAUX : 1];
-    for (int j = 0; j < NP; j++)
-        p[j] = par[b * par_stride + j];
-    JR::prepare(p, aux);
+    loadParameters<P>(par, b, par_stride, p, aux);
     const double rinv = g < NU ? 1. / rw[g < NU ? g : 0] : 0., sr = sqrt(rinv);
     const d4_t qd = diagonalTile<NX>(lane, qw);
     d4_t Pc = diagonalTile<NX>(lane, qfw);
@@ -117,22 +140,34 @@ __global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uR
     const int bad = waveOr(referenceNonFinite<NX, NU>(lane, t_max, Xb, Ub, K, nU));
     WAVE_SYNC();
 
-    const double h = t_max / double(K - 1) / double(steps);
+    const double dt = t_max / double(K - 1);
+    const double h = dt / double(steps);
     int kfail = bad ? K - 1 : -1; // nodes 0..kfail carry ST_NONFINITE and zeros
     for (int k = K - 1; k >= 0 && kfail < 0; k--)
     {
         if (k < K - 1)
         {
-            // ---- segment k: P(t_{k+1}) -> P(t_k), `steps` RKF78 steps ----
+            // ---- segment k: the tile from t_{k+1} to t_k, `steps` RKF78 steps ----
             loadSegment<NX, NU>(lds.seg, lane, Xb, Ub, k, foh ? k + 1 : k);
             WAVE_SYNC();
+            [[maybe_unused]] double xdot[NX];
+            if constexpr (AFFINE)
+                if (lane == NX)
+                {
+#pragma unroll
+                    for (int j = 0; j < NX; j++)
+                        xdot[j] = (lds.seg.x1[j] - lds.seg.x0[j]) / dt;
+                }
             for (int n = 0; n < steps; n++)
                 rkf78TileStep(Pc, h, [&](int s, const d4_t Ps) __attribute__((always_inline)) {
                     const double a = 1. - (double(n) + RK_C[s]) / double(steps);
                     double x[NX], u[NU], At[4], Bt[4];
-                    if (lane < NX)
+                    if (lane < NX + (AFFINE ? 1 : 0)) // AFFINE: lane NX evaluates the flow map at the same point
                         interpolateSegment(lds.seg, a, x, u);
-                    riccatiJacobian<P>(lds, lane, x, u, p, aux, At, Bt);
+                    if constexpr (AFFINE)
+                        affineJacobian<P>(lds, lane, x, u, p, aux, xdot, At, Bt);
+                    else
+                        riccatiJacobian<P>(lds, lane, x, u, p, aux, At, Bt);
                     return riccatiRhs(Ps, At, Bt, sr, qd);
                 });
         }
@@ -153,7 +188,7 @@ __global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uR
 #pragma unroll
         for (int c = 0; c < 4; c++)
             Wt = __builtin_amdgcn_mfma_f64_16x16x4f64(Bt[c], Pc[c], Wt, 0, 0, 0);
-        const double gain = rinv * Wt[0]; // lane (g, col): K[g][col]
+        const double gain = rinv * Wt[0]; // lane (g, col): K[g][col]; AFFINE, col == NX: k[g]
         int nf = isFinite(gain) ? 0 : 1;
 #pragma unroll
         for (int r = 0; r < 4; r++)
@@ -167,23 +202,46 @@ __global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uR
             Gb[(k * NU + g) * NX + col] = gain;
         if (Pb)
             storeTile<NX>(lane, Pb + k * NX * NX, Pc);
-        if (lane == 0)
+        if constexpr (AFFINE)
         {
-            status[b * K + k] = ST_OK;
-            iters[b * K + k] = (K - 1 - k) * steps;
+            if (g < NU && col == NX)
+                Fb[k * NU + g] = gain;
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (4 * r + g == NX) // row NX of the tile: [p' | s]
+                {
+                    if (pb && col < NX)
+                        pb[k * NX + col] = Pc[r];
+                    if (sb && col == NX)
+                        sb[k] = Pc[r];
+                }
         }
+        markNodeOk(lane, status + b * K, iters + b * K, k, (K - 1 - k) * steps);
     }
-    // a failed node never writes a non-finite gain: zeros and its status, for the node P went non-finite at and every earlier one
-    for (int e = lane; e < (kfail + 1) * NU * NX; e += WAVE)
-        Gb[e] = 0.;
-    if (Pb)
-        for (int e = lane; e < (kfail + 1) * NX * NX; e += WAVE)
-            Pb[e] = 0.;
-    for (int e = lane; e <= kfail; e += WAVE)
+    // a failed node never writes a non-finite value: zeros and its status, for the node the tile went non-finite at and every earlier one
+    backwardEpilogue<NX, NU>(lane, kfail, Gb, Pb, status + b * K, iters + b * K);
+    if constexpr (AFFINE)
     {
-        status[b * K + e] = ST_NONFINITE;
-        iters[b * K + e] = 0;
+        for (int e = lane; e < (kfail + 1) * NU; e += WAVE)
+            Fb[e] = 0.;
+        if (pb)
+            for (int e = lane; e < (kfail + 1) * NX; e += WAVE)
+                pb[e] = 0.;
+        if (sb)
+            for (int e = lane; e <= kfail; e += WAVE)
+                sb[e] = 0.;
     }
+}
+
+template <class P>
+__global__ void __launch_bounds__(WAVE) lqr_riccati_kernel(int K, int nU, int uRows, int steps, const double *__restrict__ X, const double *__restrict__ U,
+                                                            const double *__restrict__ T, const double *__restrict__ par, int par_stride,
+                                                            const double *__restrict__ qw, const double *__restrict__ rw, const double *__restrict__ qfw,
+                                                            double *__restrict__ G, int *__restrict__ status, int *__restrict__ iters,
+                                                            double *__restrict__ Pout)
+{
+    __shared__ RiccatiLds lds;
+    riccatiSweep<P, false>(lds, K, nU, uRows, steps, X, U, T, par, par_stride, qw, rw, qfw, G, status, iters, nullptr, Pout, nullptr, nullptr);
 }
 
 } // namespace lqr

@@ -1,5 +1,6 @@
-// What the two matrix sweeps along a trajectory share (lqr_riccati_kernel.h backwards, lqr_covariance_kernel.h forwards): the tile
-// layout, the reference segment in LDS, the Jacobian row of a lane, one RKF78 step of a tile, the scan of the inputs and two tile helpers.
+// What the matrix sweeps along a trajectory share (lqr_riccati_kernel.h and lqr_discrete_kernel.h backwards, lqr_covariance_kernel.h and
+// lqr_covariance_discrete_kernel.h forwards): the tile layout, the reference segment in LDS, the Jacobian row of a lane, one RKF78
+// step of a tile, the scan of the reference and two tile helpers.  The frame around a sweep (start, node, failure tail) is lqr_sweep_frame.h.
 //
 // THE TILE LAYOUT (stated here, referred to by both kernels).  ONE WAVEFRONT PER TRAJECTORY.  nx <= 14, so a symmetric nx x nx matrix M, padded with
 // zeros, is one 16 x 16 FP64 tile, kept in the accumulator layout of v_mfma_f64_16x16x4_f64 (lane l, register r: row (l >> 4) + 4 r, column l & 15):
@@ -8,6 +9,7 @@
 // read back from LDS as tile[(4c + g) * RT + col].  Products of such tiles are therefore matrix-core instructions with no lane exchange.
 #pragma once
 #include "lqr_kernels.h"
+#include <utility>
 
 namespace scpp
 {
@@ -68,28 +70,32 @@ __device__ __forceinline__ void jacobianRow(int r, const double *x, const double
     (void)JR::row(r, x, u, p, aux, uaux, jr);
 }
 
-// One fixed RKF78 step of a tile: T <- T + h sum_s b_s k_s, k_s = rhs(s, T + h sum_q a_sq k_q).  rhs is the caller's lambda (forced inline); the stage
-// loop is fully unrolled, so s is a constant inside it and the 13 slopes stay in registers.
-template <class Rhs>
-__device__ __forceinline__ void rkf78TileStep(d4_t &T, double h, Rhs &&rhs)
+// One fixed RKF78 step of a tile: T <- T + h sum_s b_s k_s, k_s = rhs(s, T + h sum_q a_sq k_q).  rhs is the caller's lambda (forced inline).
+// The stage loop is unrolled by the template, not by the optimiser, so the stage index is a constant by construction and the 13 slopes stay in
+// registers.  `#pragma unroll` does not promise that: with the flow map next to the Jacobian row (the affine and the moments sweep), thirteen
+// copies of Rocket2D's stage (sin and cos of two angles, twice) pass the size up to which the optimiser honours the pragma; the loop then stays a
+// loop, the stage slopes are indexed at run time and land in scratch memory (448 bytes per lane).
+template <int S, class Rhs>
+__device__ __forceinline__ void rkf78TileStage(d4_t (&kk)[RK_S], const d4_t &T, double h, Rhs &rhs)
+{
+    d4_t Ts;
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+    {
+        double acc = 0.;
+#pragma unroll
+        for (int qq = 0; qq < S; qq++)
+            if (RK_A[S][qq] != 0.)
+                acc += RK_A[S][qq] * kk[qq][r];
+        Ts[r] = T[r] + h * acc;
+    }
+    kk[S] = rhs(S, Ts);
+}
+template <class Rhs, int... S>
+__device__ __forceinline__ void rkf78TileStages(d4_t &T, double h, Rhs &rhs, std::integer_sequence<int, S...>)
 {
     d4_t kk[RK_S];
-#pragma unroll
-    for (int s = 0; s < RK_S; s++)
-    {
-        d4_t Ts;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-        {
-            double acc = 0.;
-#pragma unroll
-            for (int qq = 0; qq < s; qq++)
-                if (RK_A[s][qq] != 0.)
-                    acc += RK_A[s][qq] * kk[qq][r];
-            Ts[r] = T[r] + h * acc;
-        }
-        kk[s] = rhs(s, Ts);
-    }
+    (rkf78TileStage<S>(kk, T, h, rhs), ...);
 #pragma unroll
     for (int r = 0; r < 4; r++)
     {
@@ -100,6 +106,11 @@ __device__ __forceinline__ void rkf78TileStep(d4_t &T, double h, Rhs &&rhs)
                 acc += RK_B[s] * kk[s][r];
         T[r] += h * acc;
     }
+}
+template <class Rhs>
+__device__ __forceinline__ void rkf78TileStep(d4_t &T, double h, Rhs &&rhs)
+{
+    rkf78TileStages(T, h, rhs, std::make_integer_sequence<int, RK_S>{});
 }
 
 // this lane's finding about the trajectory's inputs: 1 when the final time, a state or an input is not finite (the caller reduces with waveOr)

@@ -3,11 +3,10 @@
 #include "../../../include/scpp_hip_lqr.h"
 #include "lqr_kernels.h"
 #include "lqr_riccati_kernel.h"
-#include "lqr_affine_launch.h"
 #include "lqr_covariance_kernel.h"
 #include "lqr_discrete_kernel.h"
 #include "lqr_covariance_discrete_kernel.h"
-#include "lqr_moments_launch.h"
+#include "lqr_sweep_launch.h"
 
 #ifdef SCPP_HIP_EMU
 #include "scpp_hip_lqr_affine.cpp" // the emulation is one translation unit (its fiber switch is a global symbol of the emulation header)
@@ -17,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 using namespace scpp;
@@ -29,20 +29,27 @@ using namespace scpp::lqr;
             return SCPP_E_HIP; \
     } while (0)
 
-// f(Plugin{}) for the plugin whose ID is `model`; SCPP_E_ARG for an id nobody registered
-template <class F, class... PL>
-static int withLqrPluginOf(LqrPluginList<PL...>, int model, F &&f)
-{
-    int rc = SCPP_E_ARG;
-    (void)((model == PL::ID ? (rc = f(PL{}), true) : false) || ...);
-    return rc;
-}
-template <class F>
-static int withLqrPlugin(int model, F &&f)
-{
-    return withLqrPluginOf(LqrPlugins{}, model, std::forward<F>(f));
-}
-
+// THE VALIDITY FLAGS: which entry point clears and sets which (everything else leaves them alone).  "products" = have_p, have_disc and the
+// trio have_ff / have_affine / affine_kept (clearGainProducts); "trio" = the three alone (clearAffineProducts).
+//
+//   entry point                                   clears                                              sets
+//   set_trajectories, set_trajectories_device     have_gains, gains_computed, products, have_cov      have_traj                    (invalidateGains)
+//   set_gains                                     have_gains, gains_computed, products, have_cov      then have_gains              (invalidateGains)
+//   set_weights, set_terminal_weights             if gains_computed: as set_trajectories              (have_qf)                    (invalidateComputedGains)
+//   set_flow_params                               have_cov, trio; if gains_computed: as above         have_par
+//   compute_gains                  after launch:  products, have_cov                                  have_gains, gains_computed
+//   compute_gains_riccati          before growTo: products;  after launch: have_cov                   have_gains, gains_computed, have_p = keep
+//   compute_gains_affine           before growTo: products;  after launch: have_cov                   have_gains, gains_computed, have_ff, have_affine,
+//                                                                                                     affine_kept = keep
+//   compute_gains_discrete         before growTo: products;  after launch: have_cov                   have_gains, gains_computed, have_disc = keep
+//   set_feedforward_terms                         have_affine, affine_kept                            have_ff
+//   set_covariance_inputs                         have_cov                                            have_cov_in
+//   propagate_covariance(_discrete) before growTo: have_cov, have_mom                                 after launch: have_cov, cov_kept = keep
+//   propagate_moments              before growTo: have_cov, have_mom                                  after launch: have_cov, have_mom, cov_kept = keep
+//   track, track_samples                          have_track, if the flight buffers had to grow       after the flights: have_track
+//
+// A call that fails before the point named leaves the flags as they were; one that fails after it (a failed growTo, a failed launch) leaves
+// them cleared and sets nothing.
 struct scpp_hip_lqr_ctx
 {
     int device = 0, model = 0, K = 0, nU = 0, uRows = 0, Bmax = 0, B = 0;
@@ -142,11 +149,31 @@ static bool allFinite(const double *v, size_t n)
     return true;
 }
 
+// the affine sweep's share of the products: feedforward terms, and what scpp_hip_lqr_download_affine hands out
+static void clearAffineProducts(scpp_hip_lqr_ctx *c)
+{
+    c->have_ff = c->have_affine = c->affine_kept = false;
+}
+
+// the products of a gain sweep, beyond the gains themselves
+static void clearGainProducts(scpp_hip_lqr_ctx *c)
+{
+    c->have_p = c->have_disc = false;
+    clearAffineProducts(c);
+}
+
+// the result of a covariance or moments sweep (have_mom is read together with have_cov only)
+static void clearSweepResult(scpp_hip_lqr_ctx *c)
+{
+    c->have_cov = false;
+}
+
 // whatever changes the trajectories or replaces the gains: no gains, no P, no covariance
 static void invalidateGains(scpp_hip_lqr_ctx *c)
 {
-    c->have_gains = c->gains_computed = c->have_p = c->have_disc = c->have_cov = false;
-    c->have_ff = c->have_affine = c->affine_kept = false;
+    c->have_gains = c->gains_computed = false;
+    clearGainProducts(c);
+    clearSweepResult(c);
 }
 
 // a change of weights or parameters: gains the library computed are stale, gains the caller supplied (scpp_hip_lqr_set_gains) stay
@@ -162,17 +189,19 @@ static int readyToLaunch(const scpp_hip_lqr_ctx *c)
     return c->have_traj && c->have_par && (c->par_rows == 1 || c->par_rows == c->B) ? SCPP_OK : SCPP_E_STATE;
 }
 
+// what became of a launch: `found` = the model has a plugin, so a kernel was enqueued
+static int enqueued(bool found)
+{
+    if (!found)
+        return SCPP_E_ARG;
+    return hipGetLastError() == hipSuccess ? SCPP_OK : SCPP_E_HIP;
+}
+
 // launch(Plugin{}) enqueues the kernel of the context's model
 template <class F>
 static int launchKernel(scpp_hip_lqr_ctx *c, F &&launch)
 {
-    const int rc = withLqrPlugin(c->model, [&](auto pl) {
-        launch(pl);
-        return 0;
-    });
-    if (rc)
-        return rc;
-    return hipGetLastError() == hipSuccess ? SCPP_OK : SCPP_E_HIP;
+    return enqueued(withLqrPlugin(c->model, launch));
 }
 
 // *n_ok = the entries of the device array `status` [n] equal to SCPP_LQR_OK (n_ok == nullptr: nothing is downloaded)
@@ -229,38 +258,98 @@ static int growFlights(scpp_hip_lqr_ctx *c, size_t F)
     return SCPP_OK;
 }
 
-// one covariance sweep per trajectory: the continuous loop's (lqr_covariance_kernel) or, with `discrete`, the node-rate hold's
-// (lqr_covariance_discrete_kernel); both take the same inputs and leave their result in the same buffers
-static int propagateCovariance(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok, bool discrete)
+// a buffer a sweep fills on request: `need` doubles (0: not asked for)
+struct KeepBuffer
 {
-    if (!c || steps < 1)
+    double **buf;
+    size_t *cap;
+    size_t need;
+};
+
+// One gain sweep (Riccati, affine, discrete), c != nullptr.  The order is the ABI's: a failed growTo leaves the products cleared and have_gains
+// as it was.  launch() enqueues the kernel and returns its code; kept() sets the flags of what this sweep keeps.
+template <class Launch, class Kept>
+static int runGainSweep(scpp_hip_lqr_ctx *c, int steps, int *n_ok, std::initializer_list<KeepBuffer> buffers, Launch &&launch, Kept &&kept)
+{
+    if (steps < 1)
         return SCPP_E_ARG;
     if (int rc = readyToLaunch(c))
         return rc;
-    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B))
-        return SCPP_E_STATE; // no gains, no initial covariance, or one for another number of trajectories
+    if (long(c->K - 1) * steps > 0x7fffffffL)
+        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
     DeviceGuard guard(c->device);
-    const size_t need = size_t(c->B) * c->K * c->nx * c->nx;
-    c->have_cov = c->have_mom = false;
-    if (keep_cov)
-        if (int rc = growTo(c, &c->cov, &c->cov_cap, need))
+    clearGainProducts(c);
+    for (const KeepBuffer &k : buffers)
+        if (int rc = growTo(c, k.buf, k.cap, k.need))
             return rc;
-    int rc = launchKernel(c, [&](auto pl) {
-        using P = decltype(pl);
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
-                               (const double *)c->par, c->par_stride, (const double *)c->G, (const int *)(c->gains_computed ? c->gstatus : nullptr),
-                               (const double *)c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, (const double *)c->cw, c->cstd, c->cin, c->cfin, c->cstatus,
-                               keep_cov ? c->cov : (double *)nullptr);
-        };
-        if (discrete)
-            go(lqr_covariance_discrete_kernel<P>);
-        else
-            go(lqr_covariance_kernel<P>);
-    });
+    if (int rc = launch())
+        return rc;
+    c->have_gains = c->gains_computed = true;
+    kept();
+    clearSweepResult(c);
+    return countOk(c, c->gstatus, size_t(c->B) * c->K, n_ok);
+}
+
+// what the moments sweep takes beyond the covariance sweep's arguments
+struct MomentsRequest
+{
+    int feedforward;
+    const double *mean0;
+    int rows;
+};
+
+// one forward sweep per trajectory: the continuous loop's covariance (lqr_covariance_kernel), with `discrete` the node-rate hold's
+// (lqr_covariance_discrete_kernel), with `mom` the continuous loop's covariance and mean (lqr_moments_kernel); all three take the covariance
+// inputs and leave the covariance in the same buffers
+static int propagateCovariance(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int *n_ok, bool discrete, const MomentsRequest *mom = nullptr)
+{
+    if (!c || steps < 1 || (mom && mom->feedforward != 0 && mom->feedforward != 1))
+        return SCPP_E_ARG;
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (mom && mom->mean0 && ((mom->rows != 1 && mom->rows != c->B) || !allFinite(mom->mean0, size_t(mom->rows) * c->nx)))
+        return SCPP_E_ARG;
+    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B) || (mom && mom->feedforward && !c->have_ff))
+        return SCPP_E_STATE; // no gains, no initial covariance, one for another number of trajectories, or no feedforward term to add
+    DeviceGuard guard(c->device);
+    const size_t Bm = size_t(c->Bmax), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
+    clearSweepResult(c);
+    c->have_mom = false;
+    if (mom && !c->m0 && (devAlloc(&c->m0, Bm * nx) | devAlloc(&c->cmean, Bm * K * nx) | devAlloc(&c->cdu, Bm * K * nu)))
+        return SCPP_E_HIP;
+    if (keep_cov)
+        if (int rc = growTo(c, &c->cov, &c->cov_cap, size_t(c->B) * K * nx * nx))
+            return rc;
+    if (mom && mom->mean0)
+    {
+        CHECK_HIP(hipMemcpyAsync(c->m0, mom->mean0, size_t(mom->rows) * nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        CHECK_HIP(hipStreamSynchronize(c->stream)); // the host array is the caller's
+    }
+    const int *gstatus = c->gains_computed ? c->gstatus : nullptr;
+    const int s0_stride = c->s0_rows == 1 ? 0 : c->nx * c->nx;
+    double *cov = keep_cov ? c->cov : nullptr;
+    int rc;
+    if (mom)
+        rc = enqueued(launchMomentsSweep(c->model, c->stream, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par, c->par_stride, c->G,
+                                         gstatus, c->s0, s0_stride, c->cw, mom->feedforward ? c->ff : nullptr, mom->mean0 ? c->m0 : nullptr,
+                                         mom->rows == 1 ? 0 : c->nx, c->cstd, c->cin, c->cfin, c->cstatus, cov, c->cmean, c->cdu));
+    else
+        rc = launchKernel(c, [&](auto pl) {
+            using P = decltype(pl);
+            auto go = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
+                                   (const double *)c->par, c->par_stride, (const double *)c->G, gstatus, (const double *)c->s0, s0_stride,
+                                   (const double *)c->cw, c->cstd, c->cin, c->cfin, c->cstatus, cov);
+            };
+            if (discrete)
+                go(lqr_covariance_discrete_kernel<P>);
+            else
+                go(lqr_covariance_kernel<P>);
+        });
     if (rc)
         return rc;
     c->have_cov = true;
+    c->have_mom = mom != nullptr;
     c->cov_kept = keep_cov != 0;
     return countOk(c, c->cstatus, size_t(c->B), n_ok);
 }
@@ -282,7 +371,7 @@ int scpp_hip_lqr_create(scpp_hip_lqr_ctx **out, int device_id, int model_id, int
     if (!out || K < 2 || batch_max < 1)
         return SCPP_E_ARG;
     *out = nullptr;
-    if (withLqrPlugin(model_id, [](auto) { return 0; }) != 0)
+    if (!withLqrPlugin(model_id, [](auto) {}))
         return SCPP_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev)
@@ -302,7 +391,6 @@ int scpp_hip_lqr_create(scpp_hip_lqr_ctx **out, int device_id, int model_id, int
         c->nu = P::Model::NU;
         c->np = P::Model::NP;
         c->nr = P::NR;
-        return 0;
     });
     if (hipStreamCreate(&c->stream) != hipSuccess)
     {
@@ -409,8 +497,8 @@ int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
     c->par_stride = (B == 1) ? 0 : c->np;
     c->par_rows = B;
     c->have_par = true;
-    c->have_cov = false;
-    c->have_ff = c->have_affine = c->affine_kept = false; // the defect of the nominal is one of THIS plant
+    clearSweepResult(c);
+    clearAffineProducts(c); // the defect of the nominal is one of THIS plant
     invalidateComputedGains(c);
     return SCPP_OK;
 }
@@ -465,8 +553,8 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
     if (rc)
         return rc;
     c->have_gains = c->gains_computed = true;
-    c->have_p = c->have_disc = c->have_cov = false;
-    c->have_ff = c->have_affine = c->affine_kept = false;
+    clearGainProducts(c);
+    clearSweepResult(c);
     return countOk(c, c->gstatus, size_t(nodes), n_ok);
 }
 
@@ -490,32 +578,20 @@ int scpp_hip_lqr_set_terminal_weights(scpp_hip_lqr_ctx *c, const double *qf)
 
 int scpp_hip_lqr_compute_gains_riccati(scpp_hip_lqr_ctx *c, int steps, int keep_p, int *n_ok)
 {
-    if (!c || steps < 1)
+    if (!c)
         return SCPP_E_ARG;
-    if (int rc = readyToLaunch(c))
-        return rc;
-    if (long(c->K - 1) * steps > 0x7fffffffL)
-        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
-    DeviceGuard guard(c->device);
-    const long nodes = long(c->B) * c->K;
-    const size_t p_need = size_t(nodes) * c->nx * c->nx;
-    c->have_p = c->have_disc = false;
-    c->have_ff = c->have_affine = c->affine_kept = false;
-    if (keep_p)
-        if (int rc = growTo(c, &c->P, &c->P_cap, p_need))
-            return rc;
-    int rc = launchKernel(c, [&](auto pl) {
-        using P = decltype(pl);
-        hipLaunchKernelGGL((lqr_riccati_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
-                           (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
-                           (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep_p ? c->P : (double *)nullptr);
-    });
-    if (rc)
-        return rc;
-    c->have_gains = c->gains_computed = true;
-    c->have_p = keep_p != 0;
-    c->have_cov = false;
-    return countOk(c, c->gstatus, size_t(nodes), n_ok);
+    const size_t nodes = size_t(c->B) * c->K;
+    return runGainSweep(
+        c, steps, n_ok, {{&c->P, &c->P_cap, keep_p ? nodes * c->nx * c->nx : 0}},
+        [&] {
+            return launchKernel(c, [&](auto pl) {
+                using P = decltype(pl);
+                hipLaunchKernelGGL((lqr_riccati_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU,
+                                   c->tT, (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
+                                   (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep_p ? c->P : (double *)nullptr);
+            });
+        },
+        [&] { c->have_p = keep_p != 0; });
 }
 
 int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *c, double *P)
@@ -532,38 +608,22 @@ int scpp_hip_lqr_download_riccati(scpp_hip_lqr_ctx *c, double *P)
 
 int scpp_hip_lqr_compute_gains_affine(scpp_hip_lqr_ctx *c, int steps, int keep, int *n_ok)
 {
-    if (!c || steps < 1)
+    if (!c)
         return SCPP_E_ARG;
-    if (int rc = readyToLaunch(c))
-        return rc;
-    if (long(c->K - 1) * steps > 0x7fffffffL)
-        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
-    DeviceGuard guard(c->device);
-    const long nodes = long(c->B) * c->K;
-    c->have_p = c->have_disc = false;
-    c->have_ff = c->have_affine = c->affine_kept = false;
-    if (int rc = growTo(c, &c->ff, &c->ff_cap, size_t(c->Bmax) * c->K * c->nu))
-        return rc;
-    if (keep)
-    {
-        if (int rc = growTo(c, &c->P, &c->P_cap, size_t(nodes) * c->nx * c->nx))
-            return rc;
-        if (int rc = growTo(c, &c->ap, &c->ap_cap, size_t(nodes) * c->nx))
-            return rc;
-        if (int rc = growTo(c, &c->as, &c->as_cap, size_t(nodes)))
-            return rc;
-    }
-    if (!launchAffineSweep(c->model, c->stream, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par, c->par_stride, c->q, c->r,
-                           c->have_qf ? c->qf : c->q, c->G, c->gstatus, c->giters, c->ff, keep ? c->P : nullptr, keep ? c->ap : nullptr,
-                           keep ? c->as : nullptr))
-        return SCPP_E_ARG;
-    if (hipGetLastError() != hipSuccess)
-        return SCPP_E_HIP;
-    c->have_gains = c->gains_computed = true;
-    c->have_ff = c->have_affine = true;
-    c->affine_kept = keep != 0;
-    c->have_cov = false;
-    return countOk(c, c->gstatus, size_t(nodes), n_ok);
+    const size_t nodes = size_t(c->B) * c->K, kept = keep ? nodes : 0;
+    return runGainSweep(
+        c, steps, n_ok,
+        {{&c->ff, &c->ff_cap, size_t(c->Bmax) * c->K * c->nu}, {&c->P, &c->P_cap, kept * c->nx * c->nx}, {&c->ap, &c->ap_cap, kept * c->nx},
+         {&c->as, &c->as_cap, kept}},
+        [&] {
+            return enqueued(launchAffineSweep(c->model, c->stream, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par, c->par_stride, c->q,
+                                              c->r, c->have_qf ? c->qf : c->q, c->G, c->gstatus, c->giters, c->ff, keep ? c->P : nullptr,
+                                              keep ? c->ap : nullptr, keep ? c->as : nullptr));
+        },
+        [&] {
+            c->have_affine = c->have_ff = true;
+            c->affine_kept = keep != 0;
+        });
 }
 
 int scpp_hip_lqr_download_affine(scpp_hip_lqr_ctx *c, double *ff, double *P, double *p, double *s)
@@ -615,39 +675,22 @@ int scpp_hip_lqr_set_feedforward(scpp_hip_lqr_ctx *c, int mode)
 
 int scpp_hip_lqr_compute_gains_discrete(scpp_hip_lqr_ctx *c, int steps, int keep, int *n_ok)
 {
-    if (!c || steps < 1)
+    if (!c)
         return SCPP_E_ARG;
-    if (int rc = readyToLaunch(c))
-        return rc;
-    if (long(c->K - 1) * steps > 0x7fffffffL)
-        return SCPP_E_ARG; // the step count behind node 0 is reported as an int32
-    DeviceGuard guard(c->device);
-    const long nodes = long(c->B) * c->K;
-    const size_t segs = size_t(c->B) * (c->K - 1);
-    c->have_p = c->have_disc = false;
-    c->have_ff = c->have_affine = c->affine_kept = false;
-    if (keep)
-    {
-        if (int rc = growTo(c, &c->P, &c->P_cap, size_t(nodes) * c->nx * c->nx))
-            return rc;
-        if (int rc = growTo(c, &c->phi, &c->phi_cap, segs * c->nx * c->nx))
-            return rc;
-        if (int rc = growTo(c, &c->gam, &c->gam_cap, segs * c->nx * c->nu))
-            return rc;
-    }
-    int rc = launchKernel(c, [&](auto pl) {
-        using P = decltype(pl);
-        hipLaunchKernelGGL((lqr_discrete_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT,
-                           (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
-                           (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep ? c->P : (double *)nullptr,
-                           keep ? c->phi : (double *)nullptr, keep ? c->gam : (double *)nullptr);
-    });
-    if (rc)
-        return rc;
-    c->have_gains = c->gains_computed = true;
-    c->have_disc = keep != 0;
-    c->have_cov = false;
-    return countOk(c, c->gstatus, size_t(nodes), n_ok);
+    const size_t nodes = keep ? size_t(c->B) * c->K : 0, segs = keep ? size_t(c->B) * (c->K - 1) : 0;
+    return runGainSweep(
+        c, steps, n_ok,
+        {{&c->P, &c->P_cap, nodes * c->nx * c->nx}, {&c->phi, &c->phi_cap, segs * c->nx * c->nx}, {&c->gam, &c->gam_cap, segs * c->nx * c->nu}},
+        [&] {
+            return launchKernel(c, [&](auto pl) {
+                using P = decltype(pl);
+                hipLaunchKernelGGL((lqr_discrete_kernel<P>), dim3(unsigned(c->B)), dim3(WAVE), 0, c->stream, c->K, c->nU, c->uRows, steps, c->tX, c->tU,
+                                   c->tT, (const double *)c->par, c->par_stride, (const double *)c->q, (const double *)c->r,
+                                   (const double *)(c->have_qf ? c->qf : c->q), c->G, c->gstatus, c->giters, keep ? c->P : (double *)nullptr,
+                                   keep ? c->phi : (double *)nullptr, keep ? c->gam : (double *)nullptr);
+            });
+        },
+        [&] { c->have_disc = keep != 0; });
 }
 
 int scpp_hip_lqr_download_discrete(scpp_hip_lqr_ctx *c, double *P, double *Phi, double *Gamma)
@@ -758,7 +801,7 @@ int scpp_hip_lqr_set_covariance_inputs(scpp_hip_lqr_ctx *c, const double *sigma0
     CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
     c->s0_rows = B;
     c->have_cov_in = true;
-    c->have_cov = false;
+    clearSweepResult(c);
     return SCPP_OK;
 }
 
@@ -774,37 +817,8 @@ int scpp_hip_lqr_propagate_covariance_discrete(scpp_hip_lqr_ctx *c, int steps, i
 
 int scpp_hip_lqr_propagate_moments(scpp_hip_lqr_ctx *c, int steps, int keep_cov, int feedforward, const double *mean0, int rows, int *n_ok)
 {
-    if (!c || steps < 1 || (feedforward != 0 && feedforward != 1))
-        return SCPP_E_ARG;
-    if (int rc = readyToLaunch(c))
-        return rc;
-    if (mean0 && ((rows != 1 && rows != c->B) || !allFinite(mean0, size_t(rows) * c->nx)))
-        return SCPP_E_ARG;
-    if (!c->have_gains || !c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B) || (feedforward && !c->have_ff))
-        return SCPP_E_STATE; // as scpp_hip_lqr_propagate_covariance, or a feedforward term asked for that the context does not hold
-    DeviceGuard guard(c->device);
-    const size_t Bm = size_t(c->Bmax), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
-    c->have_cov = c->have_mom = false;
-    if (!c->m0 && (devAlloc(&c->m0, Bm * nx) | devAlloc(&c->cmean, Bm * K * nx) | devAlloc(&c->cdu, Bm * K * nu)))
-        return SCPP_E_HIP;
-    if (keep_cov)
-        if (int rc = growTo(c, &c->cov, &c->cov_cap, size_t(c->B) * K * nx * nx))
-            return rc;
-    if (mean0)
-    {
-        CHECK_HIP(hipMemcpyAsync(c->m0, mean0, size_t(rows) * nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        CHECK_HIP(hipStreamSynchronize(c->stream)); // the host array is the caller's
-    }
-    if (!launchMomentsSweep(c->model, c->stream, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par, c->par_stride, c->G,
-                            c->gains_computed ? c->gstatus : nullptr, c->s0, c->s0_rows == 1 ? 0 : c->nx * c->nx, c->cw,
-                            feedforward ? c->ff : nullptr, mean0 ? c->m0 : nullptr, rows == 1 ? 0 : c->nx, c->cstd, c->cin, c->cfin, c->cstatus,
-                            keep_cov ? c->cov : nullptr, c->cmean, c->cdu))
-        return SCPP_E_ARG;
-    if (hipGetLastError() != hipSuccess)
-        return SCPP_E_HIP;
-    c->have_cov = c->have_mom = true;
-    c->cov_kept = keep_cov != 0;
-    return countOk(c, c->cstatus, size_t(c->B), n_ok);
+    const MomentsRequest mom = {feedforward, mean0, rows};
+    return propagateCovariance(c, steps, keep_cov, n_ok, false, &mom);
 }
 
 int scpp_hip_lqr_download_moments(scpp_hip_lqr_ctx *c, double *mean, double *input_mean)
@@ -859,7 +873,6 @@ int scpp_hip_lqr_set_input_limits(scpp_hip_lqr_ctx *c, const double *lim, int B)
     bool thrust_vector = false;
     (void)withLqrPlugin(c->model, [&](auto pl) {
         thrust_vector = decltype(pl)::THRUST_VECTOR;
-        return 0;
     });
     HostBuf<double> rows(size_t(B) * LIM_ROW);
     if (!rows.p)
