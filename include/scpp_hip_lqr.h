@@ -26,6 +26,8 @@
  *       (the Riccati sweep on the state [e; 1])                                scpp_hip_lqr_set_feedforward_terms, _set_feedforward
  *   nothing: the reference does not predict where its loop's centre goes                      scpp_hip_lqr_propagate_moments, _download_moments
  *       (the covariance sweep on the state [e; 1])
+ *   nothing: the reference's plant is never disturbed                                         scpp_hip_lqr_set_disturbance, _disturbance_normals
+ *       (process noise in the loop)
  *
  * Deviations, all deliberate:
  *   - RocketQuat gains are computed on the tangent system of the unit-quaternion constraint (13 states): the reference's 28 x 28 Hamiltonian
@@ -132,6 +134,20 @@
  *     Rocket2D (u = (gimbal, thrust)): gimbal clamped to [-angle_max, angle_max], thrust to [T_min, T_max].  A point inside the set is returned
  *     bitwise.  It is a clip: the gains do not know about it and there is no anti-windup.  Per flight: n_sat = the plant steps on which
  *     u != u_cmd in any component, max_clip = the largest |u_cmd - u|_2 met; out_u and the record hold the applied input u.
+ *   - process noise (scpp_hip_lqr_set_disturbance) is an addition to the tracking loop, off by default: the disturbed plant.  With a
+ *     disturbance set, plant step n of flight f integrates dx/dt = f(x, u) + d; n is the loop's own 0-based step counter and the step takes
+ *     t_n to t_n + time_step.  d_r = sqrt(w_r / time_step) z_r is constant over the plant step and is added to the slope of every RKF78 stage
+ *     of every substep; w_r is the intensity, in state^2 per second, that scpp_hip_lqr_set_covariance_inputs takes, z_r are independent
+ *     standard normals, and w_r == 0 gives d_r = 0.  This is the piecewise-constant realisation of white noise of intensity W = diag(w): one
+ *     step accumulates W time_step to first order.  z is a pure function of (seed, flight index, n, r) and there is no generator state:
+ *     Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with the counter (n, j, g lo32, g hi32),
+ *     j = r / 2 the pair index and g = flight_offset + f the global flight index, and the key (seed lo32, seed hi32).  From the output words
+ *     c0..c3: m1 = (uint64(c0) << 20) | (c1 >> 12), m2 likewise from c2, c3; u = (double(m) + 0.5) 2^-52, exact and strictly inside (0, 1);
+ *     rho = sqrt(-2 ln u1), z[2j] = rho cos(2 pi u2), z[2j+1] = rho sin(2 pi u2); an odd nx drops the last z.  The draw happens after u has
+ *     been decided (sat included) and before the plant step; a retired flight draws nothing more.  The record, max_dev, limits, feedback
+ *     hold, feedforward, the stop tolerance, sample fans and the non-finite retirement behave as without it, in every combination of limits,
+ *     hold and feedforward that exists without it.  Limitations: the noise is white, diagonal and held over a plant step; there is no
+ *     measurement noise, no coloured noise, and the gains know nothing of it.
  *   - scpp_hip_lqr_track_samples flies `samples` starts per trajectory: flight f of F = B samples follows trajectory f / samples (its X, U, t,
  *     gains, parameter row and limits row) from x_start[f]; trajectories and gains are neither copied nor recomputed.
  *
@@ -289,6 +305,17 @@ extern "C"
        and, for the thrust-vector models, T_min > T_max cos(angle_max).  The limits stay until they are set again (new trajectories do not
        clear them); they invalidate neither gains nor a covariance sweep, which describe the unlimited linear loop. */
     int scpp_hip_lqr_set_input_limits(scpp_hip_lqr_ctx *ctx, const double *lim /* [B or 1][3] or NULL */, int B);
+    /* process noise of the tracking loop (the definition is above): w [nx] >= 0, the diagonal of the disturbance intensity in state^2 per
+       second; flight f of a call draws with the global index flight_offset + f, so a fan split over several calls flies the flights of
+       one call.  NULL (the default) switches the noise off.  SCPP_E_ARG for a negative or non-finite w, which leaves the previous setting
+       in place.  The setting stays until it is set again; it invalidates nothing: gains and sweeps are untouched. */
+    int scpp_hip_lqr_set_disturbance(scpp_hip_lqr_ctx *ctx, const double *w /* [nx] or NULL */, unsigned long long seed,
+                                     unsigned long long flight_offset);
+    /* z [flights][steps][nx]: the normals the loop draws under `seed` for the global flights flight0 .. flight0 + flights - 1 on the plant
+       steps step0 .. step0 + steps - 1, computed on the device by the function the loop uses.  SCPP_E_ARG for flights < 1, steps < 1,
+       step0 < 0 or a NULL z.  Reads and changes no setting. */
+    int scpp_hip_lqr_disturbance_normals(scpp_hip_lqr_ctx *ctx, unsigned long long seed, unsigned long long flight0, int flights, int step0,
+                                         int steps, double *z /* [flights][steps][nx] */);
     /* B closed loops from x_start [B][nx] towards x_final [nx] along the trajectories: time_step > 0 (reference: 0.01), substeps >= 1 RKF78
        steps per plant step (reference: 20), at most max_steps >= 1 plant steps; the first n_record instances record every write_steps-th
        step.  *n_finite (optional) = loops that did not retire non-finite. */

@@ -489,6 +489,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_propagate_covariance_discrete",
     "scpp_hip_lqr_compute_gains_affine", "scpp_hip_lqr_download_affine", "scpp_hip_lqr_set_feedforward_terms", "scpp_hip_lqr_set_feedforward",
     "scpp_hip_lqr_propagate_moments", "scpp_hip_lqr_download_moments",
+    "scpp_hip_lqr_set_disturbance", "scpp_hip_lqr_disturbance_normals",
 ]
 _lqr_libs = {}
 
@@ -514,6 +515,8 @@ def load_lqr_library(path=None):
     lib.scpp_hip_lqr_track_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_void_p]
     lib.scpp_hip_lqr_set_trajectories_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.scpp_hip_lqr_set_disturbance.argtypes = [C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong]
+    lib.scpp_hip_lqr_disturbance_normals.argtypes = [C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lqr_libs[path] = lib
     return lib
 
@@ -703,8 +706,22 @@ class LqrContext:
         lim = np.ascontiguousarray(lim, dtype=np.float64).reshape(-1, 3)
         _chk(self.lib.scpp_hip_lqr_set_input_limits(self.h, _p(lim), int(lim.shape[0])), "lqr_set_input_limits")
 
+    def set_disturbance(self, w=None, seed=0, flight_offset=0):
+        """process noise of the tracking loop: w [nx] >= 0 the diagonal of the disturbance intensity (state^2 per second), `seed` the key of
+        the counter-based generator, flight f of a call draws as the global flight flight_offset + f; None switches the noise off"""
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(self.nx)
+        _chk(self.lib.scpp_hip_lqr_set_disturbance(self.h, _p(w), int(seed), int(flight_offset)), "lqr_set_disturbance")
+
+    def disturbance_normals(self, seed, flight0, flights, step0, steps):
+        """z [flights][steps][nx]: the normals the loop draws under `seed` for the global flights flight0 .. on the plant steps step0 .."""
+        z = np.zeros((max(int(flights), 0), max(int(steps), 0), self.nx))
+        _chk(self.lib.scpp_hip_lqr_disturbance_normals(self.h, int(seed), int(flight0), int(flights), int(step0), int(steps), _p(z)),
+             "lqr_disturbance_normals")
+        return z
+
     def track(self, x_start, x_final, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30):
-        x_start = np.ascontiguousarray(x_start, dtype=np.float64).reshape(-1, self.nx)
+        x_start =np.ascontiguousarray(x_start, dtype=np.float64).reshape(-1, self.nx)
         x_final = np.ascontiguousarray(x_final, dtype=np.float64).reshape(self.nx)
         n = C.c_int()
         _chk(self.lib.scpp_hip_lqr_track(self.h, _p(x_start), _p(x_final), int(x_start.shape[0]), float(time_step), int(substeps),

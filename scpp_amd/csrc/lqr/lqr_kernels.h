@@ -1,16 +1,18 @@
 // Batched LQR trajectory tracking: the two kernels behind include/scpp_hip_lqr.h.
 //   lqr_gain_kernel<Plugin>   one frozen-time LQR gain per (trajectory, node): replaces LQRTracker::LQRTracker (LQRTracker.cpp:6-28) and
 //                             ComputeLQR / careSolve / solveSchurIterative (LQR.cpp:7-109)
-//   lqr_track_kernel<Plugin, SAT, HOLD, FF>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
+//   lqr_track_kernel<Plugin, SAT, HOLD, FF, NOISE>  one closed loop per flight on the nonlinear plant: replaces the loop of SC_tracking.cpp:48-75 with
 //                             LQRTracker::getInput / interpolateGains (LQRTracker.cpp:43-65) and trajectoryData.hpp:41-78; SAT: with the
 //                             plugin's input limits in the loop (the clip of LQR_sim.cpp:55-66)
 //                             FF: with the feedforward term of the affine finite-horizon law (lqr_affine_kernel.h)
+//                             NOISE: with process noise on the plant (lqr_noise.h)
 // A component of its own: it reads the model plugins' flow maps, their generated Jacobian rows and the RKF78 tableau (csrc/common.h) and nothing
 // else of the solver; the solver's sources are not touched by it.
 #pragma once
 #include "../common.h"
 #include "../model_rocketquat.h"
 #include "../model_lander3dof.h"
+#include "lqr_noise.h"
 
 namespace scpp
 {
@@ -483,7 +485,11 @@ __global__ void __launch_bounds__(WAVE) lqr_gain_kernel(long nodes, int K, int n
 //   ff [B][K][nu] the row of the flight's trajectory, interpolated with the indices and the fraction of the gain; limits, record, stop tolerance
 //   and the non-finite retirement act on this u_cmd.  FF == false reads no ff and is the loop as it was; FF with HOLD is not defined (the host
 //   refuses it).
-template <class P, bool SAT, bool HOLD = false, bool FF = false>
+//   NOISE: the disturbed plant (scpp_hip_lqr_set_disturbance): plant step n = `steps` of flight b integrates dx/dt = f(x, u) + d with
+//   d_r = nsd[r] z_r, nsd [nx] = sqrt(w_r / time_step) (the host computes it, so every build multiplies with the same number) and z the normals
+//   of (seed, flight_offset + b, n, r); d is drawn once u is decided (sat included), is constant over the plant step and is added to the slope
+//   of every stage of every substep.  NOISE == false reads none of the three arguments and is the loop as it was.
+template <class P, bool SAT, bool HOLD = false, bool FF = false, bool NOISE = false>
 __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int K, int nU, int uRows, const double *__restrict__ X, const double *__restrict__ U, const double *__restrict__ T,
                                  const double *__restrict__ par, int par_stride, const double *__restrict__ G,
                                  const double *__restrict__ x_start, const double *__restrict__ x_final, double time_step, int substeps,
@@ -491,7 +497,8 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int
                                  double *__restrict__ out_u, double *__restrict__ out_s, int *__restrict__ out_i, double *__restrict__ rec_x,
                                  double *__restrict__ rec_u, double *__restrict__ rec_t, int *__restrict__ rec_n,
                                  const double *__restrict__ lim, int lim_stride, int *__restrict__ out_nsat, double *__restrict__ out_clip,
-                                 const double *__restrict__ ff)
+                                 const double *__restrict__ ff, const double *__restrict__ nsd, unsigned long long seed,
+                                 unsigned long long flight_offset)
 {
     static_assert(!(FF && HOLD), "the held loop's offset is another recursion");
     using Model = typename P::Model;
@@ -628,6 +635,16 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int
                 max_clip = clip > max_clip ? clip : max_clip;
             }
         }
+        double d[NOISE ? NX : 1];
+        if constexpr (NOISE)
+            for (int j = 0; 2 * j < NX; j++)
+            {
+                double z0, z1;
+                noiseNormalPair(seed, flight_offset + (unsigned long long)(b), uint32_t(steps), uint32_t(j), z0, z1);
+                d[2 * j] = nsd[2 * j] * z0;
+                if (2 * j + 1 < NX)
+                    d[2 * j + 1] = nsd[2 * j + 1] * z1;
+            }
         // scpp::simulate(model, time_step, u, u, x)   (simulation.cpp:25-42: RKF78, fixed steps; the input is constant over the step)
         double yn[NX];
         for (int j = 0; j < NX; j++)
@@ -648,6 +665,9 @@ __global__ void __launch_bounds__(WAVE) lqr_track_kernel(int B, int samples, int
                     ys[j] = yn[j] + h * acc;
                 }
                 Model::template systemFlowMap<double>(ys, u, p, kk[s]);
+                if constexpr (NOISE)
+                    for (int j = 0; j < NX; j++)
+                        kk[s][j] += d[j];
             }
             for (int j = 0; j < NX; j++)
             {

@@ -47,6 +47,7 @@ using namespace scpp::lqr;
 //   propagate_covariance(_discrete) before growTo: have_cov, have_mom                                 after launch: have_cov, cov_kept = keep
 //   propagate_moments              before growTo: have_cov, have_mom                                  after launch: have_cov, have_mom, cov_kept = keep
 //   track, track_samples                          have_track, if the flight buffers had to grow       after the flights: have_track
+//   set_disturbance, disturbance_normals          nothing                                             nothing (have_noise is a setting, not a result)
 //
 // A call that fails before the point named leaves the flags as they were; one that fails after it (a failed growTo, a failed launch) leaves
 // them cleared and sets nothing.
@@ -103,6 +104,14 @@ struct scpp_hip_lqr_ctx
     double *lim = nullptr;
     int lim_rows = 0; // 1 (shared) or the number of trajectories
     bool have_lim = false;
+    // process noise (scpp_hip_lqr_set_disturbance): the intensities stay on the host; every flight call turns them into sqrt(w / time_step)
+    // with its own time step (noise_sd, which lives as long as the context because it is copied asynchronously) and uploads that row to nsd,
+    // allocated by the first call that sets some
+    static constexpr int NOISE_MAX_NX = 32;
+    double noise_w[NOISE_MAX_NX] = {}, noise_sd[NOISE_MAX_NX] = {};
+    double *nsd = nullptr;
+    unsigned long long noise_seed = 0, noise_offset = 0;
+    bool have_noise = false;
 };
 
 template <class T>
@@ -444,7 +453,7 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as, c->m0, c->cmean, c->cdu};
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as, c->m0, c->cmean, c->cdu, c->nsd};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -900,6 +909,56 @@ int scpp_hip_lqr_set_input_limits(scpp_hip_lqr_ctx *c, const double *lim, int B)
     return SCPP_OK;
 }
 
+int scpp_hip_lqr_set_disturbance(scpp_hip_lqr_ctx *c, const double *w, unsigned long long seed, unsigned long long flight_offset)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!w)
+    {
+        c->have_noise = false;
+        return SCPP_OK;
+    }
+    if (c->nx > scpp_hip_lqr_ctx::NOISE_MAX_NX)
+        return SCPP_E_UNSUPPORTED;
+    for (int i = 0; i < c->nx; i++)
+        if (!std::isfinite(w[i]) || w[i] < 0.)
+            return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    if (!c->nsd && devAlloc(&c->nsd, size_t(c->nx)))
+        return SCPP_E_HIP;
+    for (int i = 0; i < c->nx; i++)
+        c->noise_w[i] = w[i];
+    c->noise_seed = seed;
+    c->noise_offset = flight_offset;
+    c->have_noise = true;
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_disturbance_normals(scpp_hip_lqr_ctx *c, unsigned long long seed, unsigned long long flight0, int flights, int step0, int steps,
+                                     double *z)
+{
+    if (!c || flights < 1 || steps < 1 || step0 < 0 || !z)
+        return SCPP_E_ARG;
+    const size_t items = size_t(flights) * size_t(steps), n = items * size_t(c->nx);
+    const size_t blocks = (items + WAVE - 1) / WAVE;
+    if (blocks > 0x7fffffffu)
+        return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    double *dz = nullptr;
+    if (devAlloc(&dz, n))
+        return SCPP_E_HIP;
+    int rc = launchKernel(c, [&](auto pl) {
+        hipLaunchKernelGGL((lqr_noise_kernel<decltype(pl)::Model::NX>), dim3(unsigned(blocks)), dim3(WAVE), 0, c->stream, seed, flight0, long(flights),
+                           unsigned(step0), steps, dz);
+    });
+    if (rc == SCPP_OK && hipMemcpyAsync(z, dz, n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = SCPP_E_HIP;
+    if (hipStreamSynchronize(c->stream) != hipSuccess)
+        rc = SCPP_E_HIP;
+    (void)hipFree(dz);
+    return rc;
+}
+
 int scpp_hip_lqr_set_stop_tolerance(scpp_hip_lqr_ctx *c, double stop_tol)
 {
     if (!c || !(stop_tol >= 0.) || !std::isfinite(stop_tol))
@@ -962,6 +1021,12 @@ int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *c, const double *x_start, const
     }
     CHECK_HIP(hipMemcpyAsync(c->xs, x_start, size_t(B) * c->nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHECK_HIP(hipMemcpyAsync(c->xf, x_final, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (c->have_noise)
+    {
+        for (int j = 0; j < c->nx; j++)
+            c->noise_sd[j] = std::sqrt(c->noise_w[j] / time_step);
+        CHECK_HIP(hipMemcpyAsync(c->nsd, c->noise_sd, size_t(c->nx) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     if (!c->have_lim)
     {
         CHECK_HIP(hipMemsetAsync(c->onsat, 0, size_t(B) * sizeof(int), c->stream));
@@ -976,9 +1041,32 @@ int scpp_hip_lqr_track_samples(scpp_hip_lqr_ctx *c, const double *x_start, const
                                (const double *)c->par, c->par_stride, (const double *)c->G, (const double *)c->xs, (const double *)c->xf, time_step,
                                substeps, c->stop_tol, max_steps, n_record, write_steps, rec_cap, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
                                (const double *)c->lim, c->lim_rows == 1 ? 0 : LIM_ROW, c->onsat, c->oclip,
-                               (const double *)(c->ffmode ? c->ff : nullptr));
+                               (const double *)(c->ffmode ? c->ff : nullptr), (const double *)(c->have_noise ? c->nsd : nullptr), c->noise_seed,
+                               c->noise_offset);
         };
-        if (c->ffmode)
+        if (c->have_noise)
+        {
+            // the disturbed plant: the same six loops, NOISE = true
+            if (c->ffmode)
+            {
+                if (c->have_lim)
+                    go(lqr_track_kernel<P, true, false, true, true>);
+                else
+                    go(lqr_track_kernel<P, false, false, true, true>);
+            }
+            else if (c->hold)
+            {
+                if (c->have_lim)
+                    go(lqr_track_kernel<P, true, true, false, true>);
+                else
+                    go(lqr_track_kernel<P, false, true, false, true>);
+            }
+            else if (c->have_lim)
+                go(lqr_track_kernel<P, true, false, false, true>);
+            else
+                go(lqr_track_kernel<P, false, false, false, true>);
+        }
+        else if (c->ffmode)
         {
             if (c->have_lim)
                 go(lqr_track_kernel<P, true, false, true>);

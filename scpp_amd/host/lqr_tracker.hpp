@@ -294,6 +294,15 @@ public:
         feedforward_on = on;
     }
     bool feedforwardOn() const { return feedforward_on; }
+    // process noise on the plant (scpp_hip_lqr_set_disturbance): w, the diagonal of the disturbance intensity, one entry per state (state^2 per
+    // second); empty: none (the default).  Flight f draws as the global flight flight_offset + f of `seed`: the same seed flies the same
+    // flights.  White, diagonal, held over a plant step; the gains do not know about it.  Stays until it is set again.
+    void setDisturbance(const std::vector<double> &w, unsigned long long seed = 0, unsigned long long flight_offset = 0)
+    {
+        if (!w.empty() && w.size() != size_t(Model::state_dim))
+            throw std::invalid_argument("LQRTracker::setDisturbance: one intensity per state");
+        check(scpp_hip_lqr_set_disturbance(ctx, w.empty() ? nullptr : w.data(), seed, flight_offset), "scpp_hip_lqr_set_disturbance");
+    }
     // regulator mode (scpp_hip_lqr_set_stop_tolerance) and user-supplied gains [B][K], for LQRAlgorithm::simulate
     void setStopTolerance(double tol) { check(scpp_hip_lqr_set_stop_tolerance(ctx, tol), "scpp_hip_lqr_set_stop_tolerance"); }
     void setGains(const std::vector<feedback_matrix_t> &G)

@@ -32,6 +32,8 @@
 //   --samples N         : N flights per trajectory (scpp_hip_lqr_track_samples): flight 0 of trajectory b from the initial state the trajectory
 //                         was solved for, flights 1 .. N-1 from states drawn by the same randomisation (instances batch + b (N - 1) + s - 1 of
 //                         --seed); the trajectories and gains are neither copied nor recomputed
+//   --disturbance       : process noise on the plant (scpp_hip_lqr_set_disturbance): w = disturbance_std^2 from LQR.info, the generator keyed
+//                         by --seed.  Without the vector in LQR.info it is refused before anything is solved.  Also writes x_end.txt
 // Writes <out>/output/<Model>/SC_tracking/<time>/0/{X,U,t}.txt of instance 0 (every 30th step, like write_steps of the reference) and prints
 // gains/s, tracked plant steps/s and the distribution of the final error.
 #include <algorithm>
@@ -55,7 +57,7 @@ int main(int argc, char **argv)
     std::string config = "../scpp_amd/config", out = "..";
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
-    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false, no_feedforward = false, mean = false;
+    bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false, no_feedforward = false, mean = false, disturbance = false;
     int covariance_steps = 5, samples = 1, mean_steps = 0;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
@@ -133,6 +135,8 @@ int main(int argc, char **argv)
             mean_steps = std::atoi(next());
         else if (!std::strcmp(argv[i], "--saturate"))
             saturate = true;
+        else if (!std::strcmp(argv[i], "--disturbance"))
+            disturbance = true;
         else if (!std::strcmp(argv[i], "--samples"))
         {
             samples = std::atoi(next());
@@ -163,6 +167,18 @@ int main(int argc, char **argv)
         Model::setParameterFolder(config);
         auto model = std::make_shared<Model>();
         model->loadParameters();
+        std::vector<double> noise_w;
+        if (disturbance)
+        {
+            noise_w = scpp::LQRTracker::loadOptionalVector("disturbance_std");
+            if (noise_w.empty())
+            {
+                std::fprintf(stderr, "--disturbance: %s/LQR.info has no disturbance_std vector\n", Model::getParameterFolder().c_str());
+                return 2;
+            }
+            for (double &v : noise_w)
+                v *= v;
+        }
 
         std::vector<Model::state_vector_t> x_inits;
         if (batch <= 0)
@@ -256,6 +272,8 @@ int main(int argc, char **argv)
         tracker.setFeedbackHold(hold_node);
         if (gain_opts.affine && no_feedforward)
             tracker.setFeedforward(false);
+        if (disturbance)
+            tracker.setDisturbance(noise_w, seed, 0);
 
         // start simulation
         scpp::lqr_track_result_t sim;
@@ -279,6 +297,8 @@ int main(int argc, char **argv)
             std::printf("Feedforward: %s\n", tracker.feedforwardOn() ? "on (u_cmd = u_ref - K_t (x - x_ref) - k_t)" : "off (--no-feedforward: the riccati loop)");
         if (samples > 1)
             std::printf("Sample fan: %d flights per trajectory, %zu flights\n", samples, F);
+        if (disturbance)
+            std::printf("Disturbance: process noise W = diag(disturbance_std)^2 held over each plant step, seed %llu\n", seed);
         if (saturate)
         {
             size_t clipped = 0;
@@ -314,7 +334,7 @@ int main(int argc, char **argv)
                 for (size_t j = 0; j < NU; j++)
                     ff << tracker.feedforward[k * NU + j] << (j + 1 < NU ? ", " : "\n");
         }
-        if (saturate || samples > 1)
+        if (saturate || samples > 1 || disturbance)
         {
             // the final state of every flight, one per row, round-trip precision
             std::ofstream fx(outputPath / "x_end.txt");

@@ -238,7 +238,7 @@ class LQRTracker:
         self.ctx.set_input_limits(lim)
 
     def track(self, x_start, x_final=None, time_step=0.01, substeps=20, max_steps=None, n_record=0, write_steps=30, samples=1, hold="step",
-              feedforward=None):
+              feedforward=None, disturbance=None, seed=0, flight_offset=0):
         """The loop of SC_tracking.cpp:48-75 on the device, `samples` flights per trajectory from x_start [B * samples][nx] (flight f follows
         trajectory f // samples; samples = 1: one flight per trajectory).  Returns x, u, t, steps, status, err0, err1 (|x - x_final| at
         start / end), max_dev (largest |x - x_ref|), n_sat (plant steps on which the input limits clipped), max_clip (largest
@@ -246,9 +246,15 @@ class LQRTracker:
         hold="step" (the default): the feedback term changes on every plant step; hold="node": du = -G[i] (x - x_ref) is latched at the
         first plant step of segment i and held over it (the loop horizon="discrete" designs for).
         feedforward: True applies u_cmd = u_ref - K_t (x - x_ref) - k_t with the terms of the affine sweep, False flies without them; None
-        (the default) means on exactly when the gains held came from the affine sweep.  Together with hold="node" it is refused."""
+        (the default) means on exactly when the gains held came from the affine sweep.  Together with hold="node" it is refused.
+        disturbance: the diagonal of a process-noise intensity W ([nx], state^2 per second, what covariance() takes); None (the default)
+        flies the undisturbed plant.  Plant step n of flight f then integrates dx/dt = f(x, u) + d with d_r = sqrt(w_r / time_step) z_r held
+        over the step, z standard normals that are a pure function of (seed, flight_offset + f, n, r): the same seed gives the same flights,
+        and a fan split over several calls with flight_offset = the flights flown so far is the fan of one call.  White, diagonal and held
+        over a plant step; no measurement noise, no coloured noise, and the gains do not know about it."""
         if hold not in ("step", "node"):
             raise ValueError(f"hold = {hold!r}: 'step' or 'node'")
+        self.ctx.set_disturbance(disturbance, seed, flight_offset)
         self.ctx.set_feedback_hold(1 if hold == "node" else 0)
         self.ctx.set_feedforward(1 if self._feedforward_on(feedforward) else 0)
         x_final = self.model.p.x_final if x_final is None else x_final
@@ -369,7 +375,8 @@ class LQRSim:
         """as LQRTracker.setInputLimits, for the loops of run(); starts as the algorithm's setting"""
         self.input_limits = lim
 
-    def run(self, x_start, x_final=None, n_record=0, write_steps=30, substeps=20):
+    def run(self, x_start, x_final=None, n_record=0, write_steps=30, substeps=20, disturbance=None, seed=0, flight_offset=0):
+        """disturbance, seed, flight_offset: process noise on the plant, as LQRTracker.track takes it"""
         a = self.alg
         assert a.initialized
         x_start = np.asarray(x_start, dtype=np.float64).reshape(-1, a.model.state_dim)
@@ -380,6 +387,7 @@ class LQRSim:
         trk.setGains(np.tile(a.K, (B, 2, 1, 1)))
         trk.ctx.set_stop_tolerance(self.stop_tol)
         trk.setInputLimits(self.input_limits)
-        out = trk.track(x_start, x_final, self.time_step, substeps, None, n_record, write_steps)
+        out = trk.track(x_start, x_final, self.time_step, substeps, None, n_record, write_steps, disturbance=disturbance, seed=seed,
+                        flight_offset=flight_offset)
         trk.close()
         return out

@@ -2,8 +2,7 @@
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
     python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--covariance-discrete STEPS]
-                             [--affine STEPS] [--moments STEPS]
-                              [--affine STEPS] [--out FILE]
+                             [--affine STEPS] [--moments STEPS] [--disturbance] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
 segment), the same N flights under those gains.  It only ADDS keys (riccati_*); the others keep their meaning.
@@ -48,7 +47,16 @@ the split of the final error: |m(T)| with and without the term (where the linear
 node), |X[K-1] - x_final| (the nominal's own last node against the target) and the flown |x(T) - X[K-1]| of the default leg's flights under
 the same gains, each as 5 / 50 / 95 % over the trajectories.
 
-The flight call of the saturate and samples legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
+--disturbance (measure(disturbance=True)) flies, right after the default leg and under its frozen-time gains, the N flights of the default leg
+with process noise on the plant (LQRTracker.track(disturbance=w); w is the covariance leg's intensity: 1 % of the initial variance per
+second) and once more without it, timed the same way IN THE SAME RUN.  It only ADDS keys (disturbance_*): the two flight-call times and
+their ratio, plant steps/s with and without noise, and the status counts.  Together with --samples N[,..] and --covariance STEPS it also
+flies a fan of N (the first of the list) disturbed flights per trajectory, all from the start the trajectory was solved from, and reports the
+fan's sample standard deviation of the final position (per trajectory, over its N flights) next to the covariance sweep's under the same
+gains, the same w and sigma0 = 0: 5 / 50 / 95 % over the trajectories of both and of their ratio, and the pooled ratio sqrt(mean fan
+variance / mean sweep variance).
+
+The flight call of the saturate, samples and disturbance legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
 best of --repeat.
 """
 import argparse
@@ -65,7 +73,7 @@ import scpp_amd  # noqa: E402
 
 
 def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None,
-            covariance_discrete=None, affine=None, moments=None):
+            covariance_discrete=None, affine=None, moments=None, disturbance=False):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -93,6 +101,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
     sat = saturate_leg(trk, x0, repeat) if saturate else {}
     if samples:
         sat["samples_legs"] = [samples_leg(trk, x0, int(N), repeat, bool(saturate)) for N in samples]
+    if disturbance:
+        sat.update(disturbance_leg(trk, x0, repeat, int(samples[0]) if samples else 0, int(covariance or 0)))
     ric = riccati_leg(trk, x0, int(riccati), repeat) if riccati else {}
     if covariance:
         ric.update(covariance_leg(trk, int(covariance), repeat, "riccati" if riccati else "frozen"))
@@ -166,6 +176,49 @@ def saturate_leg(trk, x0, repeat):
         "saturate_final_error_p5_p50_p95": final_errors(on), "saturate_off_final_error_p5_p50_p95": final_errors(off),
         "saturate_off_n_sat_total": int(off["n_sat"].sum()),
     }
+
+
+def disturbance_leg(trk, x0, repeat, N, cov_steps, seed=20261020):
+    """the default leg's flights with process noise on the plant and without it, timed the same way on the same starts; with N and cov_steps
+    a fan of N disturbed flights per trajectory from the trajectory's own start against the covariance sweep from sigma0 = 0"""
+    sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
+    w = 0.01 * sd * sd  # the covariance leg's disturbance intensity
+    trk.setInputLimits(None)
+    trk.ctx.set_disturbance(None)
+    t_off, off = time_flights(trk, x0, 1, repeat)
+    trk.ctx.set_disturbance(w, seed, 0)
+    t_on, on = time_flights(trk, x0, 1, repeat)
+    steps = int(on["steps"].sum())
+    res = {
+        "disturbance_intensity": [float(v) for v in w], "disturbance_seed": int(seed),
+        "disturbance_flight_call_s": t_on, "disturbance_off_flight_call_s": t_off, "disturbance_over_off": t_on / t_off,
+        "disturbance_plant_steps": steps, "disturbance_plant_steps_per_s": steps / t_on,
+        "disturbance_off_plant_steps": int(off["steps"].sum()), "disturbance_off_plant_steps_per_s": float(off["steps"].sum() / t_off),
+        "disturbance_flights_completed": int((on["status"] == 0).sum()), "disturbance_flights_nonfinite": int((on["status"] == -2).sum()),
+        "disturbance_final_error_p5_p50_p95": final_errors(on), "disturbance_off_final_error_p5_p50_p95": final_errors(off),
+    }
+    if N > 1 and cov_steps > 0:
+        nx = x0.shape[1]
+        t_fan, fan = time_flights(trk, np.repeat(x0, N, axis=0), N, repeat)
+        trk.ctx.set_covariance_inputs(np.zeros((nx, nx)), w)
+        n_ok = trk.ctx.propagate_covariance(cov_steps)
+        o = trk.ctx.download_covariance()
+        done = (fan["status"].reshape(-1, N) == 0).all(axis=1) & (o["status"] != -2)
+        pos = fan["x"].reshape(-1, N, nx)[done][:, :, 1:4]  # RocketQuat: states 1..3 are the position
+        fan_var = pos.var(axis=1, ddof=1).sum(axis=1)
+        sweep_var = (o["state_std"][done, -1, 1:4] ** 2).sum(axis=1)
+        pct = lambda v: [float(q) for q in np.percentile(v, [5, 50, 95])] if v.size else []  # noqa: E731
+        res.update({
+            "disturbance_fan_samples": N, "disturbance_fan_flights": int(fan["x"].shape[0]), "disturbance_fan_flight_call_s": t_fan,
+            "disturbance_fan_plant_steps_per_s": float(fan["steps"].sum() / t_fan), "disturbance_fan_trajectories_compared": int(done.sum()),
+            "disturbance_sweep_steps_per_segment": cov_steps, "disturbance_sweep_status_ok": int(n_ok),
+            "disturbance_fan_final_position_std_p5_p50_p95": pct(np.sqrt(fan_var)),
+            "disturbance_sweep_final_position_std_p5_p50_p95": pct(np.sqrt(sweep_var)),
+            "disturbance_fan_over_sweep_p5_p50_p95": pct(np.sqrt(fan_var / sweep_var)),
+            "disturbance_fan_over_sweep_pooled": float(np.sqrt(fan_var.mean() / sweep_var.mean())) if done.any() else None,
+        })
+    trk.ctx.set_disturbance(None)
+    return res
 
 
 def samples_leg(trk, x0, N, repeat, saturate):
@@ -418,11 +471,12 @@ if __name__ == "__main__":
     ap.add_argument("--covariance-discrete", type=int, default=0, help="RKF78 steps per segment of the held loop's covariance leg (0: no such leg)")
     ap.add_argument("--affine", type=int, default=0, help="RKF78 steps per segment of the affine leg (0: no such leg)")
     ap.add_argument("--moments", type=int, default=0, help="RKF78 steps per segment of the mean-and-covariance leg (0: no such leg)")
+    ap.add_argument("--disturbance", action="store_true", help="the flights again with process noise on the plant; with --samples and --covariance also the fan against the sweep")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
                   samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete, covariance_discrete=a.covariance_discrete,
-                  affine=a.affine, moments=a.moments)
+                  affine=a.affine, moments=a.moments, disturbance=a.disturbance)
     line = json.dumps(res)
     print(line)
     if a.out:
