@@ -26,6 +26,8 @@
  *       (the Riccati sweep on the state [e; 1])                                scpp_hip_lqr_set_feedforward_terms, _set_feedforward
  *   nothing: the reference does not predict where its loop's centre goes                      scpp_hip_lqr_propagate_moments, _download_moments
  *       (the covariance sweep on the state [e; 1])
+ *   nothing: the reference's controller reads the true state                                  scpp_hip_lqr_set_measurement, scpp_hip_lqr_filter,
+ *       (the Kalman-Bucy filter and the output-feedback loop's covariance)     scpp_hip_lqr_download_filter
  *   nothing: the reference's plant is never disturbed                                         scpp_hip_lqr_set_disturbance, _disturbance_normals
  *       (process noise in the loop)
  *
@@ -295,6 +297,41 @@ extern "C"
     /* mean [B][K][nx] = m(t_k), input_mean [B][K][nu] = du_mean[k]; either pointer may be NULL.  SCPP_E_STATE unless the last sweep was
        scpp_hip_lqr_propagate_moments. */
     int scpp_hip_lqr_download_moments(scpp_hip_lqr_ctx *ctx, double *mean /* [B][K][nx] */, double *input_mean /* [B][K][nu] */);
+    /* LQG: the measurement of the filter sweep, y = H e + v with e the deviation from the reference, H [ny][nx] constant and one for all
+       trajectories, v white with intensity V = diag(v) (units measurement^2 s, the convention of the disturbance intensity w).  SCPP_E_ARG
+       unless 1 <= ny <= 16, H finite, v finite and > 0.  H == NULL clears the measurement (ny and v are not read).  Either way an earlier
+       filter result is invalidated. */
+    int scpp_hip_lqr_set_measurement(scpp_hip_lqr_ctx *ctx, const double *H /* [ny][nx] or NULL */, int ny, const double *v /* [ny] */);
+    /* one forward sweep per trajectory of the Kalman-Bucy error covariance Sg of eps = e - e^ and, with closed_loop, of the covariance Xh
+       of the estimate under the output-feedback loop du = -K_t e^:
+           dSg/dt = A Sg + Sg A' + W - Sg H' V^-1 H Sg     Sg(0) = sigma0     L(t) = Sg H' V^-1
+           dXh/dt = A_cl Xh + Xh A_cl' + Sg H' V^-1 H Sg   Xh(0) = 0          A_cl = A - B K_t
+       sigma0 and W = diag(w) are those of scpp_hip_lqr_set_covariance_inputs.  A is the open-loop Jacobian at the interpolated reference,
+       K_t the interpolated gain, the segments, holds, integrator (steps >= 1 RKF78 steps per segment, taken as given) and Jacobian rows
+       those of scpp_hip_lqr_propagate_covariance, both tiles in the same step.  Because E[e^ eps'] = 0 for these gains, the state covariance
+       of the loop is Sg + Xh; the covariance of the commanded correction at node k is G[k] Xh(t_k) G[k]', not G (Sg + Xh) G'.  Sg and Xh are
+       symmetric to the bit; with H = 0, Sg is bitwise the S of scpp_hip_lqr_propagate_covariance under zero gains and Xh is zero.  A fixed-step
+       explicit scheme: the filter's initial transient has the rate rho = max_m (H sigma0 H')_mm / v_m, and h rho <= 1/8 keeps the scheme's error
+       at the level of the other sweeps (README, "Kalman-Bucy filter"); the front ends choose steps by that rule, this call does not.
+       SCPP_E_ARG for steps < 1; SCPP_E_STATE without trajectories, flow parameters, covariance inputs (or with inputs for another number of
+       trajectories) or a measurement and, with closed_loop, without gains.  Per-trajectory status: SCPP_LQR_OK; SCPP_LQR_NONFINITE for a
+       non-finite node, input, flight time or (closed_loop) gain (zeros in every output), or a tile, gain L_k or input covariance that turned
+       non-finite in segment k (node k+1, every later node and the final matrices are zeros); with closed_loop SCPP_LQR_GAINS_INCOMPLETE as for
+       the covariance sweep.  Nothing non-finite is ever written.  *n_ok = trajectories with SCPP_LQR_OK (NULL: not counted).  keep: Sg(t_k)
+       and, with closed_loop, Xh(t_k) of every node are kept for the download.  The result is invalidated by whatever changes the
+       trajectories, the flow parameters, the covariance inputs or the measurement and, when swept with closed_loop, by whatever changes the
+       gains.  The sweep changes nothing else in the context: gains, covariance and moments results and flights are what they were. */
+    int scpp_hip_lqr_filter(scpp_hip_lqr_ctx *ctx, int steps, int closed_loop, int keep, int *n_ok);
+    /* L [B][K][nx][ny] = Sg(t_k) H' V^-1, error_std [B][K][nx] = sqrt diag Sg(t_k), final_error_cov [B][nx][nx] = Sg(T), status [B] int32,
+       error_cov [B][K][nx][nx] = Sg(t_k); of a sweep with closed_loop also state_std [B][K][nx] = sqrt diag (Sg + Xh)(t_k), input_cov
+       [B][K][nu][nu] = G[k] Xh(t_k) G[k]', final_state_cov [B][nx][nx] = (Sg + Xh)(T), estimate_cov [B][K][nx][nx] = Xh(t_k).  Any pointer may
+       be NULL.  SCPP_E_STATE before a sweep, for error_cov or estimate_cov after a sweep without keep, and for any of the last four after a
+       sweep without closed_loop. */
+    int scpp_hip_lqr_download_filter(scpp_hip_lqr_ctx *ctx, double *L /* [B][K][nx][ny] */, double *error_std /* [B][K][nx] */,
+                                     double *final_error_cov /* [B][nx][nx] */, int *status /* [B] */,
+                                     double *error_cov /* [B][K][nx][nx], keep only */, double *state_std /* [B][K][nx] */,
+                                     double *input_cov /* [B][K][nu][nu] */, double *final_state_cov /* [B][nx][nx] */,
+                                     double *estimate_cov /* [B][K][nx][nx], keep only */);
     /* regulator mode (LQRAlgorithm.cpp:11-33, LQR_sim.cpp:43-82): with stop_tol > 0 a loop also ends once |x - x_final| < stop_tol.  The
        caller sets a constant two-node "trajectory" (X = x_final, U = u_eq, t = sim_time) and the one gain of the operating point
        (scpp_hip_lqr_set_gains), so that u = -K (x - x_final) + u_eq; the same two kernels, no third.  0 (the default) switches it off. */

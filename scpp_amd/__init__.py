@@ -29,3 +29,4 @@ from ._lib import MpcOpts  # noqa: F401
 from ._lib import LqrContext, load_lqr_library  # noqa: F401
 from .lqr import (LQRAlgorithm, LQRSim, LQRTracker, load_lqr_covariance_inputs, load_lqr_terminal_weights, load_lqr_weights,  # noqa: F401
                   model_input_limits)
+from .lqr import filter_steps, load_lqr_measurement  # noqa: F401

@@ -490,6 +490,7 @@ LQR_SYMBOLS = [
     "scpp_hip_lqr_compute_gains_affine", "scpp_hip_lqr_download_affine", "scpp_hip_lqr_set_feedforward_terms", "scpp_hip_lqr_set_feedforward",
     "scpp_hip_lqr_propagate_moments", "scpp_hip_lqr_download_moments",
     "scpp_hip_lqr_set_disturbance", "scpp_hip_lqr_disturbance_normals",
+    "scpp_hip_lqr_set_measurement", "scpp_hip_lqr_filter", "scpp_hip_lqr_download_filter",
 ]
 _lqr_libs = {}
 
@@ -535,6 +536,7 @@ class LqrContext:
         self.nx, self.nu, self.np_, self.nr = (int(v.value) for v in d)
         self.nU = self.K if self.foh else self.K - 1
         self.B = 0
+        self.ny = 0  # rows of the measurement held (set_measurement)
 
     def close(self):
         if getattr(self, "h", None):
@@ -672,6 +674,42 @@ class LqrContext:
         """mean [B][K][nx] = m(t_k) and input_mean [B][K][nu] = -G[k] m(t_k) - [ff[k]] of the last moments sweep"""
         out = dict(mean=np.zeros((self.B, self.K, self.nx)), input_mean=np.zeros((self.B, self.K, self.nu)))
         _chk(self.lib.scpp_hip_lqr_download_moments(self.h, _p(out["mean"]), _p(out["input_mean"])), "lqr_download_moments")
+        return out
+
+    def set_measurement(self, H, v=None):
+        """the measurement of the filter sweep, y = H e + v: H [ny][nx] (1 <= ny <= 16), v [ny] > 0 the diagonal of the noise intensity;
+        H None clears it"""
+        if H is None:
+            _chk(self.lib.scpp_hip_lqr_set_measurement(self.h, None, 0, None), "lqr_set_measurement")
+            self.ny = 0
+            return
+        H = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, self.nx)
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(H.shape[0])
+        _chk(self.lib.scpp_hip_lqr_set_measurement(self.h, _p(H), int(H.shape[0]), _p(v)), "lqr_set_measurement")
+        self.ny = int(H.shape[0])
+
+    def filter(self, steps=5, closed_loop=False, keep=False):
+        """one Kalman-Bucy sweep per trajectory (error covariance; closed_loop: and the covariance of the estimate under the gains held);
+        returns the number of trajectories with status 0"""
+        n = C.c_int()
+        _chk(self.lib.scpp_hip_lqr_filter(self.h, int(steps), int(bool(closed_loop)), int(bool(keep)), C.byref(n)), "lqr_filter")
+        return int(n.value)
+
+    def download_filter(self, closed_loop=False, keep=False):
+        """the arrays of the last filter sweep: L, error_std, final_error_cov, status; keep: error_cov; closed_loop: state_std, input_cov,
+        final_state_cov and (keep) estimate_cov"""
+        B, K, nx, nu = self.B, self.K, self.nx, self.nu
+        out = dict(L=np.zeros((B, K, nx, self.ny)), error_std=np.zeros((B, K, nx)), final_error_cov=np.zeros((B, nx, nx)),
+                   status=np.zeros(B, dtype=np.int32))
+        if keep:
+            out["error_cov"] = np.zeros((B, K, nx, nx))
+        if closed_loop:
+            out.update(state_std=np.zeros((B, K, nx)), input_cov=np.zeros((B, K, nu, nu)), final_state_cov=np.zeros((B, nx, nx)))
+            if keep:
+                out["estimate_cov"] = np.zeros((B, K, nx, nx))
+        _chk(self.lib.scpp_hip_lqr_download_filter(self.h, *[_p(out.get(k)) for k in (
+            "L", "error_std", "final_error_cov", "status", "error_cov", "state_std", "input_cov", "final_state_cov", "estimate_cov")]),
+            "lqr_download_filter")
         return out
 
     def download_covariance(self, with_cov=False):

@@ -103,6 +103,35 @@ __device__ __forceinline__ void scanForwardInputs(int lane, double t_max, const 
     incomplete = waveOr(incomplete);
 }
 
+// the lane's share of the gain tile of node k (rows >= nu and columns >= nx zero): G[col][4c + g]
+template <int NX, int NU>
+__device__ __forceinline__ void loadGainTile(int lane, int k, const double *Gb, double (&Gt)[4])
+{
+    const int g = lane >> 4, col = lane & 15;
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        const bool in = col < NU && 4 * c + g < NX;
+        Gt[c] = in ? Gb[(k * NU + (in ? col : 0)) * NX + (in ? 4 * c + g : 0)] : 0.;
+    }
+}
+
+// G T G' = G (T G') of a symmetric tile T, 8 matrix-core instructions: register 0 of lane l is (G T G')[g][col]; Wp = T G' is handed out too
+// (register r of lane l: (T G')[4r + g][col]).  forwardNode below keeps its own copy of these lines: the kernels that call it are compiled
+// exactly as they were before this helper existed.
+__device__ __forceinline__ d4_t gainCongruence(const d4_t &Tc, const double (&Gt)[4], d4_t &Wp)
+{
+    d4_t Sk = {0., 0., 0., 0.};
+    Wp = Sk;
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        Wp = __builtin_amdgcn_mfma_f64_16x16x4f64(Tc[c], Gt[c], Wp, 0, 0, 0);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+        Sk = __builtin_amdgcn_mfma_f64_16x16x4f64(Gt[c], Wp[c], Sk, 0, 0, 0);
+    return Sk;
+}
+
 // node k: the tile, its standard deviations and the input covariance G[k] S G[k]' = G (S G')  (8 matrix-core instructions); MEAN: S G' carries
 // (G m)' in row NX, so m(t_k) and du_mean[k] = -G[k] m(t_k) - [FF[k]] come with it.  false, and nothing written, if anything is not finite.
 template <int NX, int NU, bool MEAN>

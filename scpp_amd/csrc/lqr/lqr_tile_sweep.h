@@ -113,6 +113,54 @@ __device__ __forceinline__ void rkf78TileStep(d4_t &T, double h, Rhs &&rhs)
     rkf78TileStages(T, h, rhs, std::make_integer_sequence<int, RK_S>{});
 }
 
+// The same step for N tiles that advance together (the filter sweep: the error covariance and the covariance of the estimate): rhs(s, Ts, F) fills
+// the N slopes F from the N stage tiles Ts.  Element for element the arithmetic of rkf78TileStep, so a tile whose slope does not depend on its
+// neighbours comes out bitwise as rkf78TileStep leaves it; 13 N slope tiles stay in registers by the same unrolling.
+template <int S, int N, class Rhs>
+__device__ __forceinline__ void rkf78TilesStage(d4_t (&kk)[N][RK_S], const d4_t (&T)[N], double h, Rhs &rhs)
+{
+    d4_t Ts[N], F[N];
+#pragma unroll
+    for (int t = 0; t < N; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+        {
+            double acc = 0.;
+#pragma unroll
+            for (int qq = 0; qq < S; qq++)
+                if (RK_A[S][qq] != 0.)
+                    acc += RK_A[S][qq] * kk[t][qq][r];
+            Ts[t][r] = T[t][r] + h * acc;
+        }
+    rhs(S, Ts, F);
+#pragma unroll
+    for (int t = 0; t < N; t++)
+        kk[t][S] = F[t];
+}
+template <int N, class Rhs, int... S>
+__device__ __forceinline__ void rkf78TilesStages(d4_t (&T)[N], double h, Rhs &rhs, std::integer_sequence<int, S...>)
+{
+    d4_t kk[N][RK_S];
+    (rkf78TilesStage<S, N>(kk, T, h, rhs), ...);
+#pragma unroll
+    for (int t = 0; t < N; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+        {
+            double acc = 0.;
+#pragma unroll
+            for (int s = 0; s < RK_S; s++)
+                if (RK_B[s] != 0.)
+                    acc += RK_B[s] * kk[t][s][r];
+            T[t][r] += h * acc;
+        }
+}
+template <int N, class Rhs>
+__device__ __forceinline__ void rkf78TilesStep(d4_t (&T)[N], double h, Rhs &&rhs)
+{
+    rkf78TilesStages<N>(T, h, rhs, std::make_integer_sequence<int, RK_S>{});
+}
+
 // this lane's finding about the trajectory's inputs: 1 when the final time, a state or an input is not finite (the caller reduces with waveOr)
 template <int NX, int NU>
 __device__ __forceinline__ int referenceNonFinite(int lane, double t_max, const double *Xb, const double *Ub, int K, int nU)

@@ -11,6 +11,7 @@
 #ifdef SCPP_HIP_EMU
 #include "scpp_hip_lqr_affine.cpp" // the emulation is one translation unit (its fiber switch is a global symbol of the emulation header)
 #include "scpp_hip_lqr_moments.cpp"
+#include "scpp_hip_lqr_filter.cpp"
 #endif
 
 #include <cmath>
@@ -46,6 +47,11 @@ using namespace scpp::lqr;
 //   set_covariance_inputs                         have_cov                                            have_cov_in
 //   propagate_covariance(_discrete) before growTo: have_cov, have_mom                                 after launch: have_cov, cov_kept = keep
 //   propagate_moments              before growTo: have_cov, have_mom                                  after launch: have_cov, have_mom, cov_kept = keep
+//   set_measurement                               have_filt                                           have_meas (H == NULL: cleared)
+//   filter                         before growTo: have_filt                                           after launch: have_filt, filt_loop = closed_loop,
+//                                                                                                     filt_kept = keep
+//   have_filt is also cleared by whatever changes the trajectories, the parameters or the covariance inputs and, when filt_loop, by whatever
+//   changes the gains (clearFilterResult, clearLoopFilterResult); the covariance and moments sweeps leave it alone, and the filter sweep them.
 //   track, track_samples                          have_track, if the flight buffers had to grow       after the flights: have_track
 //   set_disturbance, disturbance_normals          nothing                                             nothing (have_noise is a setting, not a result)
 //
@@ -87,6 +93,14 @@ struct scpp_hip_lqr_ctx
     // their own, allocated by the first sweep
     double *m0 = nullptr, *cmean = nullptr, *cdu = nullptr;
     bool have_mom = false; // the last sweep was the moments sweep (read together with have_cov, which everything that invalidates a sweep clears)
+    // filter sweep (scpp_hip_lqr_filter): the measurement (H [ny][nx], v [ny]; room for 16 rows) is allocated by the first
+    // scpp_hip_lqr_set_measurement, the outputs by the first sweep, the loop's by the first sweep with closed_loop, the kept tiles on request
+    double *mH = nullptr, *mv = nullptr;
+    int ny = 0;
+    double *fL = nullptr, *fes = nullptr, *ffe = nullptr, *fec = nullptr, *fss = nullptr, *fic = nullptr, *ffs = nullptr, *fxc = nullptr;
+    int *fstatus = nullptr;
+    size_t fec_cap = 0, fxc_cap = 0;
+    bool have_meas = false, have_filt = false, filt_loop = false, filt_kept = false;
     double *xs = nullptr, *xf = nullptr, *ox = nullptr, *ou = nullptr, *os = nullptr;
     int *oi = nullptr;
     double *rx = nullptr, *ru = nullptr, *rt = nullptr;
@@ -177,12 +191,26 @@ static void clearSweepResult(scpp_hip_lqr_ctx *c)
     c->have_cov = false;
 }
 
+// the result of a filter sweep
+static void clearFilterResult(scpp_hip_lqr_ctx *c)
+{
+    c->have_filt = false;
+}
+
+// the gains changed: a filter result that carries the loop's covariance went with them
+static void clearLoopFilterResult(scpp_hip_lqr_ctx *c)
+{
+    if (c->filt_loop)
+        clearFilterResult(c);
+}
+
 // whatever changes the trajectories or replaces the gains: no gains, no P, no covariance
 static void invalidateGains(scpp_hip_lqr_ctx *c)
 {
     c->have_gains = c->gains_computed = false;
     clearGainProducts(c);
     clearSweepResult(c);
+    clearLoopFilterResult(c);
 }
 
 // a change of weights or parameters: gains the library computed are stale, gains the caller supplied (scpp_hip_lqr_set_gains) stay
@@ -267,6 +295,37 @@ static int growFlights(scpp_hip_lqr_ctx *c, size_t F)
     return SCPP_OK;
 }
 
+// a group of buffers that are allocated by the first call that needs them and live as long as the context
+struct OwnedBuffer
+{
+    double **buf;
+    size_t n;
+};
+
+// every buffer of the group is allocated afterwards; nothing happens when all are.  A failed allocation frees the whole group, so a later
+// call starts over and no launch ever sees some of them.
+static int allocateTogether(std::initializer_list<OwnedBuffer> group)
+{
+    bool all = true;
+    for (const OwnedBuffer &b : group)
+        all = all && *b.buf;
+    if (all)
+        return SCPP_OK;
+    int rc = 0;
+    for (const OwnedBuffer &b : group)
+        if (!*b.buf)
+            rc |= devAlloc(b.buf, b.n);
+    if (!rc)
+        return SCPP_OK;
+    for (const OwnedBuffer &b : group)
+    {
+        if (*b.buf)
+            (void)hipFree(*b.buf);
+        *b.buf = nullptr;
+    }
+    return SCPP_E_HIP;
+}
+
 // a buffer a sweep fills on request: `need` doubles (0: not asked for)
 struct KeepBuffer
 {
@@ -296,6 +355,7 @@ static int runGainSweep(scpp_hip_lqr_ctx *c, int steps, int *n_ok, std::initiali
     c->have_gains = c->gains_computed = true;
     kept();
     clearSweepResult(c);
+    clearLoopFilterResult(c);
     return countOk(c, c->gstatus, size_t(c->B) * c->K, n_ok);
 }
 
@@ -453,7 +513,8 @@ int scpp_hip_lqr_destroy(scpp_hip_lqr_ctx *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     void *bufs[] = {c->X, c->U, c->T, c->par, c->q, c->r, c->qf, c->P, c->G, c->gstatus, c->giters, c->xs, c->xf, c->ox, c->ou, c->os, c->oi, c->rx, c->ru, c->rt, c->rn,
-                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as, c->m0, c->cmean, c->cdu, c->nsd};
+                    c->s0, c->cw, c->cstd, c->cin, c->cfin, c->cov, c->cstatus, c->onsat, c->oclip, c->lim, c->phi, c->gam, c->ff, c->ap, c->as, c->m0, c->cmean, c->cdu, c->nsd,
+                    c->mH, c->mv, c->fL, c->fes, c->ffe, c->fec, c->fss, c->fic, c->ffs, c->fxc, c->fstatus};
     for (void *p : bufs)
         if (p)
             (void)hipFree(p);
@@ -507,6 +568,7 @@ int scpp_hip_lqr_set_flow_params(scpp_hip_lqr_ctx *c, const double *par, int B)
     c->par_rows = B;
     c->have_par = true;
     clearSweepResult(c);
+    clearFilterResult(c);
     clearAffineProducts(c); // the defect of the nominal is one of THIS plant
     invalidateComputedGains(c);
     return SCPP_OK;
@@ -528,6 +590,7 @@ int scpp_hip_lqr_set_trajectories(scpp_hip_lqr_ctx *c, const double *X, const do
     c->B = B;
     c->have_traj = true;
     invalidateGains(c);
+    clearFilterResult(c);
     return SCPP_OK;
 }
 
@@ -542,6 +605,7 @@ int scpp_hip_lqr_set_trajectories_device(scpp_hip_lqr_ctx *c, const void *dX, co
     c->B = B;
     c->have_traj = true;
     invalidateGains(c);
+    clearFilterResult(c);
     return SCPP_OK;
 }
 
@@ -564,6 +628,7 @@ int scpp_hip_lqr_compute_gains(scpp_hip_lqr_ctx *c, int *n_ok)
     c->have_gains = c->gains_computed = true;
     clearGainProducts(c);
     clearSweepResult(c);
+    clearLoopFilterResult(c);
     return countOk(c, c->gstatus, size_t(nodes), n_ok);
 }
 
@@ -811,6 +876,105 @@ int scpp_hip_lqr_set_covariance_inputs(scpp_hip_lqr_ctx *c, const double *sigma0
     c->s0_rows = B;
     c->have_cov_in = true;
     clearSweepResult(c);
+    clearFilterResult(c);
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_set_measurement(scpp_hip_lqr_ctx *c, const double *H, int ny, const double *v)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!H)
+    {
+        c->have_meas = false;
+        clearFilterResult(c);
+        return SCPP_OK;
+    }
+    if (!v || ny < 1 || ny > RT || !allFinite(H, size_t(ny) * c->nx) || !allFinite(v, size_t(ny)))
+        return SCPP_E_ARG;
+    for (int m = 0; m < ny; m++)
+        if (!(v[m] > 0.))
+            return SCPP_E_ARG;
+    DeviceGuard guard(c->device);
+    if (int rc = allocateTogether({{&c->mH, size_t(RT) * c->nx}, {&c->mv, size_t(RT)}}))
+        return rc;
+    CHECK_HIP(hipMemcpyAsync(c->mH, H, size_t(ny) * c->nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipMemcpyAsync(c->mv, v, size_t(ny) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream)); // the host arrays are the caller's
+    c->ny = ny;
+    c->have_meas = true;
+    clearFilterResult(c);
+    return SCPP_OK;
+}
+
+int scpp_hip_lqr_filter(scpp_hip_lqr_ctx *c, int steps, int closed_loop, int keep, int *n_ok)
+{
+    if (!c || steps < 1)
+        return SCPP_E_ARG;
+    if (int rc = readyToLaunch(c))
+        return rc;
+    if (!c->have_cov_in || (c->s0_rows != 1 && c->s0_rows != c->B) || !c->have_meas || (closed_loop && !c->have_gains))
+        return SCPP_E_STATE; // no initial covariance, one for another number of trajectories, no measurement, or no gains to close the loop with
+    DeviceGuard guard(c->device);
+    const size_t Bm = size_t(c->Bmax), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
+    clearFilterResult(c);
+    if (int rc = allocateTogether({{&c->fL, Bm * K * nx * RT}, {&c->fes, Bm * K * nx}, {&c->ffe, Bm * nx * nx}}))
+        return rc;
+    if (!c->fstatus && devAlloc(&c->fstatus, Bm))
+    {
+        c->fstatus = nullptr;
+        return SCPP_E_HIP;
+    }
+    if (closed_loop)
+        if (int rc = allocateTogether({{&c->fss, Bm * K * nx}, {&c->fic, Bm * K * nu * nu}, {&c->ffs, Bm * nx * nx}}))
+            return rc;
+    if (keep)
+    {
+        if (int rc = growTo(c, &c->fec, &c->fec_cap, size_t(c->B) * K * nx * nx))
+            return rc;
+        if (closed_loop)
+            if (int rc = growTo(c, &c->fxc, &c->fxc_cap, size_t(c->B) * K * nx * nx))
+                return rc;
+    }
+    const int *gstatus = (closed_loop && c->gains_computed) ? c->gstatus : nullptr;
+    const int s0_stride = c->s0_rows == 1 ? 0 : c->nx * c->nx;
+    if (int rc = enqueued(launchFilterSweep(c->model, c->stream, closed_loop != 0, c->B, c->K, c->nU, c->uRows, steps, c->tX, c->tU, c->tT, c->par,
+                                            c->par_stride, c->G, gstatus, c->s0, s0_stride, c->cw, c->mH, c->mv, c->ny, c->fL, c->fes, c->ffe,
+                                            c->fstatus, keep ? c->fec : nullptr, c->fss, c->fic, c->ffs, (keep && closed_loop) ? c->fxc : nullptr)))
+        return rc;
+    c->have_filt = true;
+    c->filt_loop = closed_loop != 0;
+    c->filt_kept = keep != 0;
+    return countOk(c, c->fstatus, size_t(c->B), n_ok);
+}
+
+int scpp_hip_lqr_download_filter(scpp_hip_lqr_ctx *c, double *L, double *error_std, double *final_error_cov, int *status, double *error_cov,
+                                 double *state_std, double *input_cov, double *final_state_cov, double *estimate_cov)
+{
+    if (!c)
+        return SCPP_E_ARG;
+    if (!c->have_filt || ((error_cov || estimate_cov) && !c->filt_kept) || ((state_std || input_cov || final_state_cov || estimate_cov) && !c->filt_loop))
+        return SCPP_E_STATE;
+    DeviceGuard guard(c->device);
+    const size_t B = size_t(c->B), K = size_t(c->K), nx = size_t(c->nx), nu = size_t(c->nu);
+    const struct
+    {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } copies[] = {{L, c->fL, B * K * nx * size_t(c->ny) * sizeof(double)},
+                  {error_std, c->fes, B * K * nx * sizeof(double)},
+                  {final_error_cov, c->ffe, B * nx * nx * sizeof(double)},
+                  {status, c->fstatus, B * sizeof(int)},
+                  {error_cov, c->fec, B * K * nx * nx * sizeof(double)},
+                  {state_std, c->fss, B * K * nx * sizeof(double)},
+                  {input_cov, c->fic, B * K * nu * nu * sizeof(double)},
+                  {final_state_cov, c->ffs, B * nx * nx * sizeof(double)},
+                  {estimate_cov, c->fxc, B * K * nx * nx * sizeof(double)}};
+    for (const auto &cp : copies)
+        if (cp.dst)
+            CHECK_HIP(hipMemcpyAsync(cp.dst, cp.src, cp.bytes, hipMemcpyDeviceToHost, c->stream));
+    CHECK_HIP(hipStreamSynchronize(c->stream));
     return SCPP_OK;
 }
 

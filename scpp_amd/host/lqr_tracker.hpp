@@ -87,6 +87,40 @@ struct lqr_moments_result_t : lqr_covariance_result_t
     std::vector<double> input_mean; // [B][K][NU]  -G[k] m(t_k) - [ff[k]]: the mean correction on top of u_ref
 };
 
+// the filter sweep (scpp_hip_lqr_filter): the Kalman-Bucy error covariance Sg of the measurement y = H e + v along every trajectory and, with
+// the loop closed on the estimate (du = -K_t e^), the covariance Xh of the estimate; the state covariance of that loop is Sg + Xh.
+// sigma0, disturbance, keep: as lqr_covariance_options_t.  H: [ny][NX] row-major, one for all trajectories; measurement_noise: the diagonal
+// of V, ny entries > 0; whichever is empty: that of LQR.info's measurement_std (LQRTracker::loadMeasurement).  closed_loop < 0 (the default): exactly
+// when the tracker holds gains; 0 / 1: the filter alone / with the loop's covariance.  steps <= 0 (the default): the smallest count >= 5 with
+// h rho <= 1/8, rho = max_m (H sigma0 H')_mm / v_m, from the largest rho and dt of the batch (LQRTracker::filterSteps); above 200 the call is
+// refused (std::invalid_argument names rho, the count and the way out) and never changes the count.  A linearisation about the nominal with
+// continuous measurements and continuous feedback; no flight corresponds to it.
+struct lqr_filter_options_t
+{
+    std::vector<double> sigma0;
+    std::vector<double> disturbance;
+    std::vector<double> H;
+    std::vector<double> measurement_noise;
+    int steps = 0;
+    int closed_loop = -1;
+    bool keep = false;
+};
+
+struct lqr_filter_result_t
+{
+    std::vector<double> L;               // [B][K][NX][ny]  Sg(t_k) H' V^-1
+    std::vector<double> error_std;       // [B][K][NX]  sqrt of the diagonal of Sg(t_k)
+    std::vector<double> final_error_cov; // [B][NX][NX]
+    std::vector<double> error_cov;       // [B][K][NX][NX], keep only
+    std::vector<double> state_std;       // [B][K][NX]  sqrt of the diagonal of (Sg + Xh)(t_k); closed loop only, as the next three
+    std::vector<double> input_cov;       // [B][K][NU][NU]  G[k] Xh(t_k) G[k]'
+    std::vector<double> final_state_cov; // [B][NX][NX]
+    std::vector<double> estimate_cov;    // [B][K][NX][NX], keep only
+    std::vector<int32_t> status;         // [B]: SCPP_LQR_OK, SCPP_LQR_GAINS_INCOMPLETE, SCPP_LQR_NONFINITE
+    int n_ok = 0, ny = 0, steps = 0;
+    bool closed_loop = false;
+};
+
 class LQRTracker
 {
 public:
@@ -430,6 +464,107 @@ public:
                                                o.keep ? out.cov.data() : nullptr),
               "scpp_hip_lqr_download_covariance");
         check(scpp_hip_lqr_download_moments(ctx, out.mean.data(), out.input_mean.data()), "scpp_hip_lqr_download_moments");
+    }
+
+    static constexpr int FILTER_MIN_STEPS = 5, FILTER_MAX_STEPS = 200;
+
+    // the filter sweep's step rule: the smallest count >= 5 with h rho <= 1/8, h = dt_max / steps (a count that the rule meets to 1e-12
+    // relative is taken as meeting it); *rho_out = max_m (H sigma0 H')_mm / v_m over every sigma0 given.  Returned whatever its size.
+    static int filterSteps(const std::vector<double> &sigma0, const std::vector<double> &H, const std::vector<double> &v, double dt_max,
+                           double *rho_out = nullptr)
+    {
+        const size_t ny = v.size();
+        double rho = 0.;
+        for (size_t b = 0; b < sigma0.size() / (NX * NX); b++)
+            for (size_t m = 0; m < ny; m++)
+            {
+                double hsh = 0.;
+                for (size_t i = 0; i < NX; i++)
+                    for (size_t j = 0; j < NX; j++)
+                        hsh += H[m * NX + i] * sigma0[(b * NX + i) * NX + j] * H[m * NX + j];
+                rho = std::max(rho, hsh / v[m]);
+            }
+        if (rho_out)
+            *rho_out = rho;
+        const double need = std::ceil(8. * rho * dt_max * (1. - 1e-12));
+        if (!std::isfinite(need))
+            return FILTER_MAX_STEPS + 1;
+        return std::max(FILTER_MIN_STEPS, int(std::min(need, 2147483647.))); // the count it would take, whatever its size
+    }
+
+    // LQG analysis of every trajectory at once, on the device; changes neither gains, covariance results nor flights
+    void filter(const lqr_filter_options_t &o, lqr_filter_result_t &out)
+    {
+        const size_t B = tds.size(), K = tds[0].n_X();
+        if (o.sigma0.size() != NX * NX && o.sigma0.size() != B * NX * NX)
+            throw std::invalid_argument("LQRTracker::filter: sigma0 is one NX x NX matrix, or one per trajectory");
+        if (!o.disturbance.empty() && o.disturbance.size() != NX)
+            throw std::invalid_argument("LQRTracker::filter: disturbance needs one entry per state");
+        std::vector<double> H = o.H, v = o.measurement_noise;
+        if (H.empty() || v.empty())
+        {
+            // whichever is not given comes from LQR.info
+            std::vector<double> Hf, vf;
+            loadMeasurement(Hf, vf);
+            if (H.empty())
+                H = Hf;
+            if (v.empty())
+                v = vf;
+        }
+        if (v.empty() || H.size() != v.size() * NX)
+            throw std::invalid_argument("LQRTracker::filter: no measurement: give H [ny][NX] and measurement_noise [ny], or LQR.info a measurement_std vector");
+        const bool loop = o.closed_loop < 0 ? !gains.empty() : o.closed_loop != 0;
+        int steps = o.steps;
+        if (steps <= 0)
+        {
+            double dt_max = 0., rho = 0.;
+            for (const trajectory_data_t &td : tds)
+                dt_max = std::max(dt_max, td.t / double(K - 1));
+            steps = filterSteps(o.sigma0, H, v, dt_max, &rho);
+            if (steps > FILTER_MAX_STEPS)
+                throw std::invalid_argument("LQRTracker::filter: the initial transient has the rate rho = max (H sigma0 H')_mm / v_m = " + std::to_string(rho) +
+                                            " per second, which needs " + std::to_string(steps) + " steps per segment for h rho <= 1/8; more than " +
+                                            std::to_string(FILTER_MAX_STEPS) +
+                                            " is refused.  Give steps explicitly, or use a larger measurement_noise or a smaller sigma0.");
+        }
+        const int ny = int(v.size());
+        check(scpp_hip_lqr_set_covariance_inputs(ctx, o.sigma0.data(), int(o.sigma0.size() / (NX * NX)),
+                                                 o.disturbance.empty() ? nullptr : o.disturbance.data()),
+              "scpp_hip_lqr_set_covariance_inputs");
+        check(scpp_hip_lqr_set_measurement(ctx, H.data(), ny, v.data()), "scpp_hip_lqr_set_measurement");
+        check(scpp_hip_lqr_filter(ctx, steps, loop ? 1 : 0, o.keep ? 1 : 0, &out.n_ok), "scpp_hip_lqr_filter");
+        out.ny = ny;
+        out.steps = steps;
+        out.closed_loop = loop;
+        out.L.assign(B * K * NX * size_t(ny), 0.);
+        out.error_std.assign(B * K * NX, 0.);
+        out.final_error_cov.assign(B * NX * NX, 0.);
+        out.status.assign(B, 0);
+        out.error_cov.assign(o.keep ? B * K * NX * NX : 0, 0.);
+        out.state_std.assign(loop ? B * K * NX : 0, 0.);
+        out.input_cov.assign(loop ? B * K * NU * NU : 0, 0.);
+        out.final_state_cov.assign(loop ? B * NX * NX : 0, 0.);
+        out.estimate_cov.assign(loop && o.keep ? B * K * NX * NX : 0, 0.);
+        auto ptr = [](std::vector<double> &a) { return a.empty() ? nullptr : a.data(); };
+        check(scpp_hip_lqr_download_filter(ctx, out.L.data(), out.error_std.data(), out.final_error_cov.data(), out.status.data(), ptr(out.error_cov),
+                                           ptr(out.state_std), ptr(out.input_cov), ptr(out.final_state_cov), ptr(out.estimate_cov)),
+              "scpp_hip_lqr_download_filter");
+    }
+
+    // H [ny][NX] and v [ny] from the optional measurement_std vector of LQR.info (one entry per state: the square root of the noise intensity of a
+    // sensor that reads that state, 0: not measured): H selects the non-zero entries, v_m = std_m^2; both empty without the vector
+    static void loadMeasurement(std::vector<double> &H, std::vector<double> &v)
+    {
+        H.clear();
+        v.clear();
+        const std::vector<double> sd = loadOptionalVector("measurement_std");
+        for (size_t j = 0; j < sd.size(); j++)
+            if (sd[j] != 0.)
+            {
+                H.resize(H.size() + NX, 0.);
+                H[H.size() - NX + j] = 1.;
+                v.push_back(sd[j] * sd[j]);
+            }
     }
 
     // the optional vector `name` of LQR.info (initial_std, disturbance_std: one entry per state); empty without the file or the entry

@@ -34,6 +34,12 @@
 //                         --seed); the trajectories and gains are neither copied nor recomputed
 //   --disturbance       : process noise on the plant (scpp_hip_lqr_set_disturbance): w = disturbance_std^2 from LQR.info, the generator keyed
 //                         by --seed.  Without the vector in LQR.info it is refused before anything is solved.  Also writes x_end.txt
+//   --filter            : also the LQG analysis along every trajectory (scpp_hip_lqr_filter): the Kalman-Bucy filter of the sensors that
+//                         measurement_std of LQR.info describes (one entry per state, 0: not measured) and the covariance of the loop closed
+//                         on its estimate, under those gains; sigma0 and W as for --covariance.  --filter-steps n RKF78 steps per segment
+//                         (default: the smallest count >= 5 with h rho <= 1/8, refused above 200).  Without the vector in LQR.info it is
+//                         refused before anything is solved.  Writes error_std.txt, filter_gain.txt (one node per row, the nx x ny matrix
+//                         row-major), lqg_state_std.txt and lqg_input_cov.txt of instance 0 next to X.txt
 // Writes <out>/output/<Model>/SC_tracking/<time>/0/{X,U,t}.txt of instance 0 (every 30th step, like write_steps of the reference) and prints
 // gains/s, tracked plant steps/s and the distribution of the final error.
 #include <algorithm>
@@ -58,7 +64,8 @@ int main(int argc, char **argv)
     int batch = 0, K = 0, device = 0;
     scpp::lqr_gain_options_t gain_opts;
     bool covariance = false, saturate = false, hold_node = false, covariance_hold_node = false, no_feedforward = false, mean = false, disturbance = false;
-    int covariance_steps = 5, samples = 1, mean_steps = 0;
+    int covariance_steps = 5, samples = 1, mean_steps = 0, filter_steps = 0;
+    bool filter = false;
     double time_step = 0.01;
     unsigned long long seed = 20260927ull;
     for (int i = 1; i < argc; i++)
@@ -133,6 +140,10 @@ int main(int argc, char **argv)
             mean = true;
         else if (!std::strcmp(argv[i], "--mean-steps"))
             mean_steps = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--filter"))
+            filter = true;
+        else if (!std::strcmp(argv[i], "--filter-steps"))
+            filter_steps = std::atoi(next());
         else if (!std::strcmp(argv[i], "--saturate"))
             saturate = true;
         else if (!std::strcmp(argv[i], "--disturbance"))
@@ -178,6 +189,17 @@ int main(int argc, char **argv)
             }
             for (double &v : noise_w)
                 v *= v;
+        }
+        std::vector<double> meas_H, meas_v;
+        if (filter)
+        {
+            scpp::LQRTracker::loadMeasurement(meas_H, meas_v);
+            if (meas_v.empty())
+            {
+                std::fprintf(stderr, "--filter: %s/LQR.info has no measurement_std vector (or none of its entries is non-zero)\n",
+                             Model::getParameterFolder().c_str());
+                return 2;
+            }
         }
 
         std::vector<Model::state_vector_t> x_inits;
@@ -254,6 +276,29 @@ int main(int argc, char **argv)
                 std::printf("Mean: %d RKF78 steps per segment, covariance and mean in %.2f ms, feedforward term %s (%d of %zu trajectories with status 0)\n",
                             co.steps, 1e3 * (seconds() - t0), ff ? "in" : "not in", mom.n_ok, N);
             }
+        }
+
+        // the filter of the sensors LQR.info describes, and the loop closed on its estimate
+        scpp::lqr_filter_result_t filt;
+        if (filter)
+        {
+            constexpr size_t NX = Model::state_dim;
+            scpp::lqr_filter_options_t fo;
+            fo.steps = filter_steps;
+            fo.H = meas_H;
+            fo.measurement_noise = meas_v;
+            const std::vector<double> sd0 = scpp::LQRTracker::loadOptionalVector("initial_std");
+            fo.disturbance = scpp::LQRTracker::loadOptionalVector("disturbance_std");
+            fo.sigma0.assign(NX * NX, 0.);
+            for (size_t j = 0; j < sd0.size(); j++)
+                fo.sigma0[j * NX + j] = sd0[j] * sd0[j];
+            for (double &v : fo.disturbance)
+                v *= v;
+            t0 = seconds();
+            tracker.filter(fo, filt);
+            const double t_filt = seconds() - t0;
+            std::printf("Filter: %d measurements, %d RKF78 steps per segment, %zu right-hand sides in %.2f ms (%d of %zu trajectories with status 0)\n",
+                        filt.ny, filt.steps, N * (r.td[0].n_X() - 1) * size_t(filt.steps) * 13, 1e3 * t_filt, filt.n_ok, N);
         }
 
         // the starts: `samples` per trajectory, the first of each the state its trajectory was solved for
@@ -379,6 +424,23 @@ int main(int argc, char **argv)
                         fu << mom.input_mean[k * NU + j] << (j + 1 < NU ? ", " : "\n");
                 }
             }
+        }
+        if (filter)
+        {
+            // instance 0, one node per row, round-trip precision
+            constexpr size_t NX = Model::state_dim, NU = Model::input_dim;
+            const size_t Kn = r.td[0].n_X(), nL = NX * size_t(filt.ny);
+            auto rows = [&](const char *name, const std::vector<double> &a, size_t n) {
+                std::ofstream f(outputPath / name);
+                f.precision(17);
+                for (size_t k = 0; k < Kn; k++)
+                    for (size_t j = 0; j < n; j++)
+                        f << a[k * n + j] << (j + 1 < n ? ", " : "\n");
+            };
+            rows("error_std.txt", filt.error_std, NX);
+            rows("filter_gain.txt", filt.L, nL);
+            rows("lqg_state_std.txt", filt.state_std, NX);
+            rows("lqg_input_cov.txt", filt.input_cov, NU * NU);
         }
         std::printf("output: %s\n", outputPath.string().c_str());
     }

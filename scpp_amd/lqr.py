@@ -47,6 +47,39 @@ def load_lqr_covariance_inputs(model):
     return tuple(np.array(ps.load_vector(k, model.state_dim), dtype=np.float64) if ps.has(k) else None for k in ("initial_std", "disturbance_std"))
 
 
+def load_lqr_measurement(model):
+    """(H [ny][nx], v [ny]) from the optional measurement_std vector of <model>/LQR.info: one entry per state, the square root of the
+    measurement-noise intensity of a sensor that reads that state, 0 for a state that is not measured.  H selects the non-zero entries,
+    v_m = std_m^2.  (None, None) when the file or the vector is absent, or no entry is non-zero."""
+    path = os.path.join(model.getParameterFolder(), "LQR.info")
+    if not os.path.exists(path):
+        return None, None
+    ps = ParameterServer(path)
+    if not ps.has("measurement_std"):
+        return None, None
+    sd = np.array(ps.load_vector("measurement_std", model.state_dim), dtype=np.float64)
+    idx = np.flatnonzero(sd)
+    if idx.size == 0:
+        return None, None
+    H = np.zeros((idx.size, model.state_dim))
+    H[np.arange(idx.size), idx] = 1.0
+    return H, sd[idx] ** 2
+
+
+FILTER_MIN_STEPS, FILTER_MAX_STEPS, FILTER_STEP_RATIO = 5, 200, 8.0
+
+
+def filter_steps(sigma0, H, v, dt_max):
+    """(steps, rho) of the filter sweep's step rule: rho = max_m (H sigma0 H')_mm / v_m, the rate of the filter's initial transient, over
+    every sigma0 given; steps = the smallest count >= 5 with h rho <= 1/8, h = dt_max / steps (a count that the rule meets to 1e-12
+    relative is taken as meeting it).  The count is returned whatever its size; LQRTracker.filter refuses above 200."""
+    H = np.asarray(H, dtype=np.float64)
+    S = np.asarray(sigma0, dtype=np.float64).reshape(-1, H.shape[1], H.shape[1])
+    rho = float((np.einsum("mi,bij,mj->bm", H, S, H) / np.asarray(v, dtype=np.float64)[None, :]).max())
+    need = FILTER_STEP_RATIO * rho * float(dt_max)
+    return max(FILTER_MIN_STEPS, int(math.ceil(need * (1.0 - 1e-12))) if math.isfinite(need) else FILTER_MAX_STEPS + 1), rho
+
+
 def si_flow_params(model):
     """the flow-map parameters in SI units (the tracker flies the dimensional plant)"""
     try:
@@ -300,6 +333,42 @@ class LQRTracker:
         out = self.ctx.download_covariance(keep)
         out.update(self.ctx.download_moments())
         out["n_ok"] = n_ok
+        return out
+
+    def filter(self, sigma0, disturbance=None, H=None, measurement_noise=None, steps=None, closed_loop=None, keep=False):
+        """LQG analysis along every trajectory, one forward sweep per trajectory on the device: the Kalman-Bucy filter of the measurement
+        y = H e + v (H [ny][nx], one for all trajectories; v white with intensity diag(measurement_noise)), and with closed_loop the
+        output-feedback loop du = -K_t e^ under the gains held:
+            dSg/dt = A Sg + Sg A' + W - Sg H' V^-1 H Sg,    Sg(0) = sigma0,   L = Sg H' V^-1      (error covariance of e - e^)
+            dXh/dt = A_cl Xh + Xh A_cl' + Sg H' V^-1 H Sg,  Xh(0) = 0                             (covariance of the estimate)
+        sigma0 and disturbance as in covariance().  H / measurement_noise None: those of LQR.info's measurement_std
+        (load_lqr_measurement).  closed_loop None: exactly when the tracker has gains.  steps None: the smallest count >= 5 with
+        h rho <= 1/8, rho = max_m (H sigma0 H')_mm / v_m, from the largest rho and dt of the batch (filter_steps); a count above 200 is
+        refused, never changed.  Returns L [B][K][nx][ny], error_std [B][K][nx], final_error_cov, status [B], n_ok, steps, with
+        closed_loop state_std (sqrt diag (Sg + Xh)), input_cov (G[k] Xh G[k]') and final_state_cov, and with keep=True error_cov and
+        estimate_cov [B][K][nx][nx].  A linearisation about the nominal with continuous measurements and continuous feedback; the tracking
+        kernel flies no estimator, so no flight corresponds to it."""
+        if H is None or measurement_noise is None:
+            Hf, vf = load_lqr_measurement(self.model)
+            if Hf is None:
+                raise ValueError("no measurement: pass H and measurement_noise, or give LQR.info a measurement_std vector")
+            H, measurement_noise = (Hf if H is None else H), (vf if measurement_noise is None else measurement_noise)
+        H = np.asarray(H, dtype=np.float64).reshape(-1, self.model.state_dim)
+        v = np.asarray(measurement_noise, dtype=np.float64).reshape(-1)
+        if closed_loop is None:
+            closed_loop = self._gains is not None
+        if steps is None:
+            steps, rho = filter_steps(sigma0, H, v, float(self.t.max()) / (self.K - 1))
+            if steps > FILTER_MAX_STEPS:
+                raise ValueError(
+                    f"filter: the initial transient has the rate rho = max (H sigma0 H')_mm / v_m = {rho:.6g} per second, which needs {steps} "
+                    f"steps per segment for h rho <= 1/{FILTER_STEP_RATIO:g}; more than {FILTER_MAX_STEPS} is refused.  Pass steps explicitly, "
+                    "or use a larger measurement_noise or a smaller sigma0.")
+        self.ctx.set_covariance_inputs(sigma0, disturbance)
+        self.ctx.set_measurement(H, v)
+        n_ok = self.ctx.filter(steps, closed_loop, keep)
+        out = self.ctx.download_filter(closed_loop, keep)
+        out["n_ok"], out["steps"] = n_ok, int(steps)
         return out
 
     def close(self):

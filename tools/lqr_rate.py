@@ -1,7 +1,7 @@
 """LQR tracking at size (for the record and for rocprofv3): N RocketQuat trajectories from SCvxAlgorithm.solveStream, one LQR gain per node
 (N x 50), N tracked flights of the nonlinear plant from the randomised initial states.  Prints one JSON line.
 
-    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--covariance-discrete STEPS]
+    python tools/lqr_rate.py [--n 8192] [--repeat 3] [--riccati STEPS] [--covariance STEPS] [--saturate] [--samples N[,N..]] [--discrete STEPS] [--covariance-discrete STEPS] [--filter STEPS]
                              [--affine STEPS] [--moments STEPS] [--disturbance] [--out FILE]
 
 --riccati STEPS (measure(riccati=STEPS)) adds a leg with the finite-horizon gains: one Riccati sweep per trajectory (STEPS RKF78 steps per
@@ -56,6 +56,13 @@ fan's sample standard deviation of the final position (per trajectory, over its 
 gains, the same w and sigma0 = 0: 5 / 50 / 95 % over the trajectories of both and of their ratio, and the pooled ratio sqrt(mean fan
 variance / mean sweep variance).
 
+--filter STEPS (measure(filter=STEPS)) adds, right after the covariance leg and under the same gains, the filter sweep
+(LqrContext.filter, STEPS RKF78 steps per segment, taken as given): the Kalman-Bucy error covariance alone (filter_alone_*) and together with
+the covariance of the estimate under the loop closed on it (filter_loop_*), next to the covariance sweep on the same gains and inputs IN THE
+SAME RUN (filter_covariance_wall_s: the yardstick).  sigma0 and w are the covariance leg's; the sensors read r, v and q (ny = 10) with
+v_m = 8 h (H sigma0 H')_mm, h = the largest dt of the batch / STEPS, which is h rho = 1/8, the front ends' step rule.  It only ADDS keys:
+wall times, right-hand sides/s (one counted per stage), status counts and non-finite values of both variants.
+
 The flight call of the saturate, samples and disturbance legs is timed at the context (upload of the starts, the kernel, the synchronisation; no download of results),
 best of --repeat.
 """
@@ -73,7 +80,7 @@ import scpp_amd  # noqa: E402
 
 
 def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, riccati=None, covariance=None, saturate=False, samples=(), discrete=None,
-            covariance_discrete=None, affine=None, moments=None, disturbance=False):
+            covariance_discrete=None, affine=None, moments=None, disturbance=False, filter=None):
     model = scpp_amd.RocketQuat().loadParameters()
     x0 = model.randomized_initial_states(n)
     alg = scpp_amd.SCvxAlgorithm(model, K=K, batch_max=min(slots, n), library=library).initialize()
@@ -106,6 +113,8 @@ def measure(n=8192, K=50, repeat=3, slots=4096, library=None, lqr_library=None, 
     ric = riccati_leg(trk, x0, int(riccati), repeat) if riccati else {}
     if covariance:
         ric.update(covariance_leg(trk, int(covariance), repeat, "riccati" if riccati else "frozen"))
+    if filter:
+        ric.update(filter_leg(trk, int(filter), repeat, "riccati" if riccati else "frozen"))
     if discrete:
         ric.update(discrete_leg(trk, x0, int(discrete), repeat))
     if covariance_discrete:
@@ -425,6 +434,48 @@ def covariance_leg(trk, steps, repeat, law):
     }
 
 
+def filter_leg(trk, steps, repeat, law):
+    """the filter sweep on the tracker's trajectories, alone and with the loop's tile under the gains held, and the covariance sweep next to it"""
+    sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
+    sigma0, w = np.diag(sd * sd), 0.01 * sd * sd
+    nx = sd.size
+    H = np.zeros((10, nx))
+    H[np.arange(10), np.arange(1, 11)] = 1.0  # RocketQuat: states 1..10 are r, v, q
+    h = float(np.nanmax(trk.t)) / (trk.K - 1) / steps
+    v = 8.0 * h * np.einsum("mi,ij,mj->m", H, sigma0, H)
+    trk.ctx.set_covariance_inputs(sigma0, w)
+    trk.ctx.set_measurement(H, v)
+    rhs = trk.B * (trk.K - 1) * steps * 13
+
+    def timed(sweep):
+        sweep()  # warm
+        tc = []
+        for _ in range(repeat):
+            t = time.perf_counter()
+            n_ok = sweep()  # returns after the status of every trajectory is on the host
+            tc.append(time.perf_counter() - t)
+        return min(tc), n_ok
+
+    t_c, ok_c = timed(lambda: trk.ctx.propagate_covariance(steps))
+    res = {"filter_steps_per_segment": steps, "filter_gains": law, "filter_measurements": 10, "filter_rhs": int(rhs), "filter_trajectories": int(trk.B),
+           "filter_covariance_wall_s": t_c, "filter_covariance_status_ok": int(ok_c), "filter_covariance_rhs_per_s": rhs / t_c}
+    for key, loop in (("filter_alone", False), ("filter_loop", True)):
+        t_f, n_ok = timed(lambda: trk.ctx.filter(steps, loop))
+        o = trk.ctx.download_filter(loop)
+        st = o["status"]
+        ok = st != -2
+        std = o["state_std" if loop else "error_std"]
+        pos = np.sqrt((std[ok, -1, 1:4] ** 2).sum(axis=1))
+        res.update({
+            f"{key}_wall_s": t_f, f"{key}_over_covariance": t_f / t_c, f"{key}_rhs_per_s": rhs / t_f, f"{key}_status_ok": int(n_ok),
+            f"{key}_status_gains_incomplete": int((st == 2).sum()), f"{key}_status_nonfinite": int((st == -2).sum()),
+            f"{key}_status_other": int(((st != 0) & (st != 2) & (st != -2)).sum()),
+            f"{key}_nonfinite_values": int(sum((~np.isfinite(a)).sum() for k, a in o.items() if k != "status")),
+            f"{key}_final_position_std_p5_p50_p95": [float(q) for q in np.percentile(pos, [5, 50, 95])] if pos.size else [],
+        })
+    return res
+
+
 def covariance_discrete_leg(trk, steps, repeat, law):
     """the covariance sweep of the held loop on the tracker's trajectories under the gains it holds, and the continuous sweep next to it"""
     sd = np.maximum(0.01 * np.nanmax(np.abs(trk.X), axis=(0, 1)), 1e-3)
@@ -472,11 +523,12 @@ if __name__ == "__main__":
     ap.add_argument("--affine", type=int, default=0, help="RKF78 steps per segment of the affine leg (0: no such leg)")
     ap.add_argument("--moments", type=int, default=0, help="RKF78 steps per segment of the mean-and-covariance leg (0: no such leg)")
     ap.add_argument("--disturbance", action="store_true", help="the flights again with process noise on the plant; with --samples and --covariance also the fan against the sweep")
+    ap.add_argument("--filter", type=int, default=0, help="RKF78 steps per segment of the filter leg (0: no such leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = measure(a.n, repeat=a.repeat, riccati=a.riccati, covariance=a.covariance, saturate=a.saturate,
                   samples=[int(v) for v in a.samples.split(",") if v], discrete=a.discrete, covariance_discrete=a.covariance_discrete,
-                  affine=a.affine, moments=a.moments, disturbance=a.disturbance)
+                  affine=a.affine, moments=a.moments, disturbance=a.disturbance, filter=a.filter)
     line = json.dumps(res)
     print(line)
     if a.out:
